@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- image-text pairs/s (forward + backward) of the CLIP contrastive-training hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" = one `loss = clip(text, image, return_loss=True); loss.backward()` on one synthetic batch (randint tokens,
@@ -10,9 +10,16 @@ when N > 1.  Workload = BASELINE.json configs[1]: default CLIP (dim 512, depth 6
 patch dropout 0.5), bf16, local batch 1024, InfoNCE; weak scaling (1024 pairs per GPU, global batch 1024 N, the global
 similarity matrix sharded over the ranks after an RCCL all-gather of the latents).
 
-Prints ONE JSON line on rank 0 (metric/value/unit/..., plus `roofline` for the dominant kernel family -- the MFMA GEMM --
-measured live with HIP events on the launch stream during the timed steps, and `cpu_baseline` = the CPU oracle timed on a
-bounded sample on this host's cores, rank 0 at N = 1 only).
+Prints ONE JSON line on rank 0 (metric/value/unit/ms_per_step/...).  A plain run sets up, warms up, times the K steps and prints
+the line; everything else is measured only with `--full`: `roofline` for the dominant kernel family -- the MFMA GEMM -- and the
+other families, measured with HIP events on the launch stream over K more single-stream steps, `head_32k`, `clock_mhz`, the dense
+last text layer beside the line, `device_state`, the communication attribution at N > 1, and `cpu_baseline` = the CPU oracle timed
+on a bounded sample on this host's cores (rank 0 at N = 1 only).
+
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32): `loss`, and `grad.<parameter name>`
+for every parameter gradient -- whole up to 65536 elements, else a fixed seeded sample of its flattened entries (the same positions
+in every run with the same arguments; at most 64 MB in all).  Inputs, weights and the random streams are seeded, so two builds can
+be compared output for output.
 """
 import argparse
 import json
@@ -259,12 +266,33 @@ def head_32k_probe(dev, iters=10, warm=3):
     return out
 
 
+def dump_outputs(model, loss, out_dir, max_elems=1 << 16, budget_bytes=60 << 20):
+    """what a caller of the timed step receives after it -- the loss and every parameter gradient -- as float32 .npy files in `out_dir`.
+    A gradient larger than the per-tensor share of the budget is represented by a fixed sample of its flattened entries: indices drawn
+    once from a generator seeded by the tensor's size, so the same positions are written in every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    named = [(n, p.grad) for n, p in model.named_parameters() if p.grad is not None]
+    per = max(1, min(max_elems, budget_bytes // 4 // max(len(named) + 1, 1)))
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    for n, g in named:
+        flat = g.detach().reshape(-1)
+        if flat.numel() > per:
+            idx = torch.randint(0, flat.numel(), (per,), generator=torch.Generator().manual_seed(flat.numel())).sort().values
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(out_dir, f"grad.{n}.npy"), flat.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=1024, help="pairs per GPU")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline line: per-family roofline probe pass, head_32k, clock "
+                    "under load, the dense last layer beside the line, device telemetry, the communication attribution (N > 1), the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's loss and parameter gradients "
+                    "(float32 .npy; large gradients as a fixed seeded sample) into DIR")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-head-probe", action="store_true", help="skip roofline.families.head_32k (the contrastive head's kernels at the 4096 x 32768 x 512 rank block)")
     ap.add_argument("--no-probe", action="store_true", help="skip the per-launch GEMM event probe pass after the timed region")
@@ -391,9 +419,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    probe = None if args.no_probe else ops.KernelProbe()
+    probe = ops.KernelProbe() if args.full and not args.no_probe else None
     fence()
-    tele0 = gpu_telemetry(local_rank)
+    tele0 = gpu_telemetry(local_rank) if args.full else None
     ms0 = torch.cuda.memory_stats(dev)
     # one event per step boundary on the main stream (every side stream of a step is joined back before its loss.backward() returns):
     # the per-step spread of the timed region, so that one slow step, a slow box and a slow kernel can be told apart from the line
@@ -406,13 +434,15 @@ def main():
     fence()
     ms1 = torch.cuda.memory_stats(dev)
     elapsed = time.perf_counter() - t0
-    tele1 = gpu_telemetry(local_rank)
+    tele1 = gpu_telemetry(local_rank) if args.full else None
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     loss_val = float(loss.detach())
+    if args.dump_outputs and rank == 0:                          # (before any further step: the last TIMED step's results)
+        dump_outputs(model, loss, args.dump_outputs)
 
     vt = model.visual_transformer
     n_keep = max(1, int(vt.num_patches * (1 - vt.patch_dropout.prob)))
@@ -439,7 +469,7 @@ def main():
                                "patch dropout 0.5, " + ("DCL" if args.dcl else "InfoNCE") + ("" if not args.simsiam else " + SimSiam side loss") +
                                ("" if not args.causal else ", causal text encoder") + ", fwd+bwd" +
                                ("; the last text layer computes only the CLS row the head reads (the same loss and gradients up to bf16 rounding order; "
-                                "the dense layer is timed in `dense_last_layer`)" if text_pooled else ""),
+                                "the dense layer is timed in `dense_last_layer` with --full)" if text_pooled else ""),
                    "workload_tag": workload_tag, "local_batch": b, "global_batch": b * world, "parallelism": f"dp{world}",
                    # the CLS head reads one row of the text encoding: the last text layer's row-wise part (to_out, feed-forward, norm_out) runs on
                    # that row only -- same loss, same gradient of every parameter as the dense layer (tests: pruned_rows_equal_dense, the reference
@@ -451,12 +481,15 @@ def main():
         # GPU time between consecutive step boundaries of the timed region (events on the main stream, this rank) and the device state
         # sysfs reports right before / right after it; the shader clock sustained UNDER the load is `clock_mhz` (probe pass, below)
         "step_ms": {"min": round(step_ms[0], 3), "median": round(step_ms[len(step_ms) // 2], 3), "max": round(step_ms[-1], 3)},
-        "device_state": {"before": tele0, "after": tele1},
         # hipMalloc calls inside the timed region (0 once the caching allocator is warm) and the peak footprint
         "allocator": {"device_mallocs_in_timed_region": int(ms1.get("num_device_alloc", 0) - ms0.get("num_device_alloc", 0)),
                       "peak_reserved_gb": round(ms1.get("reserved_bytes.all.peak", 0) / 1e9, 2)},
     }
+    if args.full:
+        out["device_state"] = {"before": tele0, "after": tele1}
     if world > 1:
+        out["comm"] = {"backend": dist.get_backend(), "pg_world_size": dist.get_world_size()}
+    if world > 1 and args.full:
         # Communication attribution: who is in the job, what the wire carries and how long the COMPUTE stream stalls for
         # it -- an event pair on the current stream around every wait for a collective (x_clip_amd.distributed.CommProbe), over `steps` more
         # steps of the same workload.  The prediction the first real 1 -> 8 curve is to be judged against: DESIGN.md section 4.
@@ -485,6 +518,7 @@ def main():
             "measured": "HIP events on the compute stream around every wait for a collective (max over ranks), " + str(args.steps) + " extra steps; "
                         "exposed = what the step pays, 0 when the collective finished under the kernels issued meanwhile",
         }
+    if world > 1:
         # Self-verification of the multi-rank step: every rank evaluates the SAME global-batch loss (its partial sums are
         # all-reduced) and, after GradSync, holds the SAME averaged gradients -- bit for bit, they come out of one all-reduce.  The last
         # step's loss and a checksum of three gradients (first text layer's to_qkv, the patch embedding, the temperature: one from each
@@ -633,7 +667,7 @@ def main():
         out["clock_mhz"] = ({"min": round(clk[0]), "median": round(clk[len(clk) // 2]), "max": round(clk[-1]), "samples": len(clk),
                              "measured": "xclip_clock_sample: shader cycles over 200 us windows that start with every 8th GEMM launch of two extra steps (one wave on a side stream beside the running kernels)"}
                             if clk else None)
-    if text_pooled and not args.no_dense_compare:
+    if args.full and text_pooled and not args.no_dense_compare:
         # the same step with the reference's dense last text layer (every token row through to_out / feed-forward / norm_out), for the record
         # (side streams as in the timed region: the probe pass above switched them off)
         if not args.no_overlap:
@@ -655,7 +689,7 @@ def main():
         model.prune_unused_rows = True
         out["dense_last_layer"] = {"ms_per_step": round(dense_s / nd * 1e3, 3), "value": round(b * world * nd / dense_s, 2), "steps": nd,
                                    "note": "CLIP.prune_unused_rows = False (bench.py --dense-last-layer): the same loss and gradients up to bf16 rounding order"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # the reference itself where it can be imported (north_star: "the reference CPU forward+backward timed on the host cores of the same
         # box"), kind "reference"; the GPU boxes hold no /root/reference: there the oracle port is timed, kind "port" 
         ref_line = reference_cpu_baseline()

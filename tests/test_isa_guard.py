@@ -51,8 +51,9 @@ NO_SPILL = ["gemm8_kernel<false, 0>", "gemm8_kernel<false, 1>", "gemm8_kernel<tr
 
 
 @pytest.fixture(scope="module")
-def isa():
+def isa(tmp_path_factory):
     import isa_scan
+    isa_scan.OUT = str(tmp_path_factory.mktemp("isa"))         # (the assembly in a directory of this session: a fixed shared path may belong to another user)
     return isa_scan.scan_product()
 
 

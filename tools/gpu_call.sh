@@ -29,6 +29,7 @@ for TASK in "$@"; do
       timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee gpurun_out/${TAG}_smoke.log;;
     bench)
       [ -z "$ARG" ] && REST="--steps 20 --warmup 5"
+      REST="--full $REST"                                     # the whole line: roofline, families, dense last layer, CPU baseline
       timeout 900 python bench.py $REST > gpurun_out/${TAG}_bench${SUF}.log 2>&1; tail -1 gpurun_out/${TAG}_bench${SUF}.log | cut -c1-2600;;
     trace)
       [ -z "$ARG" ] && REST="--steps 5 --warmup 1"
