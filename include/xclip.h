@@ -20,7 +20,7 @@ extern "C" {
 #endif
 
 enum { XCLIP_F32 = 0, XCLIP_BF16 = 1 };
-#define XCLIP_ABI_VERSION 23
+#define XCLIP_ABI_VERSION 24
 
 int xclip_abi_version(void);
 const char* xclip_last_error(void);
@@ -327,6 +327,31 @@ int xclip_neg_cosine_fwd(const void* p, const void* z, int64_t rows, int64_t dim
                          float* loss_accum, int dtype, void* stream);
 int xclip_neg_cosine_bwd(const void* p, const void* z, const float* cosv, const float* rp, const float* rz, const float* gmul, float coef,
                          void* dp, int64_t rows, int64_t dim, int dtype, void* stream);
+
+/* ---- the optimizer step: clip by global norm + AdamW with fp32 master weights (x_clip_amd/optim.py FusedAdamW) ------------------------
+ * The reference has no optimizer; these three replace torch.nn.utils.clip_grad_norm_ (gradnorm_partial + optim_prepare: without its read
+ * of the norm on the host) and torch.optim.AdamW.step (adamw_step: one pass instead of a chain of foreach launches), for ALL parameters of
+ * a model at once.  `table`: device array of 48-byte chunk records, one per piece of <= 65536 elements of a parameter
+ * (csrc/kernels/optim.h OptChunk: parameter pointer, gradient pointer, element offset into the flat fp32 state arrays, count, dtypes,
+ * parameter index, first-chunk flag); element counts and base addresses need NOT be multiples of 16 bytes here (scalar tail / scalar
+ * chunk).  `state_block`: 32 device bytes (OptBlock: grad_norm f32, clip_coef f32, found_nonfinite, step, skipped as int32), zeroed once
+ * by the caller.  step_base [parameters] int32, initialised to -1: the global step count at which a parameter got its first gradient.
+ *   gradnorm_partial: partials[c] = sum of squares of chunk c's gradient, c in [chunk0, chunk0 + count), all of dtype g_dtype; fixed
+ *     summation order, no atomics (bit-reproducible).
+ *   optim_prepare: sums partials[0 .. n_chunks) in a fixed order -> grad_norm, clip_coef = clip ? min(1, max_norm / (norm + 1e-6)) : 1.
+ *     Norm finite: step += 1, and step_base[absent[i]] += 1 (parameters with state but no gradient in this step keep their own count).
+ *     Otherwise found_nonfinite = 1, skipped += 1 and nothing else changes.  Nothing is read back to the host.
+ *   adamw_step: chunks [chunk0, chunk0 + count), all of (p_dtype, g_dtype), with ONE set of hyper-parameters (a param group): when
+ *     found_nonfinite the kernel returns at once; else g *= clip_coef; w *= 1 - lr wd; m = b1 m + (1 - b1) g; v = b2 v + (1 - b2) g^2;
+ *     w -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps), t = step - step_base[parameter] (torch.optim.AdamW's order).
+ *     bf16 parameters: w is master[state_off + i] (fp32) and the parameter is written as its round-to-nearest-even bf16; fp32
+ *     parameters are w themselves and `master` may be NULL.  exp_avg / exp_avg_sq / master: the flat fp32 arrays, 16-byte aligned. */
+int xclip_gradnorm_partial(const void* table, int64_t chunk0, int64_t count, int g_dtype, float* partials, void* stream);
+int xclip_optim_prepare(const float* partials, int64_t n_chunks, float max_norm, int clip, void* state_block, int32_t* step_base,
+                        const int32_t* absent, int64_t n_absent, void* stream);
+int xclip_adamw_step(const void* table, int64_t chunk0, int64_t count, int p_dtype, int g_dtype, float* exp_avg, float* exp_avg_sq,
+                     float* master, const void* state_block, int32_t* step_base, double lr, double beta1, double beta2, double eps,
+                     double weight_decay, void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_int64, c_uint64, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_uint64, c_void_p
 
 import torch  # noqa: F401  (must be imported first: the .so binds to torch's libamdhip64)
 
@@ -20,7 +20,7 @@ LIB_PATH = os.path.join(_HERE, "libxclip_hip.so")
 _lib = None
 _is_emulator = False
 
-P, I, L, F, U = c_void_p, c_int, c_int64, c_float, c_uint64
+P, I, L, F, U, D = c_void_p, c_int, c_int64, c_float, c_uint64, c_double
 
 _SIGNATURES = {
     "xclip_abi_version": (c_int, []),
@@ -89,9 +89,12 @@ _SIGNATURES = {
     "xclip_simloss_combine": (c_int, [P, L, L, P, P, P, F, P]),
     "xclip_simloss_fwd": (c_int, [P, P, L, L, L, F, P, L, I, F, P, P, P, P, I, P]),
     "xclip_simloss_grad": (c_int, [P, P, L, L, L, F, P, L, I, F, F, F, P, I, P, P, P, L, P, I, P]),
+    "xclip_gradnorm_partial": (c_int, [P, L, L, I, P, P]),
+    "xclip_optim_prepare": (c_int, [P, L, F, I, P, P, P, L, P]),
+    "xclip_adamw_step": (c_int, [P, L, L, I, I, P, P, P, P, P, D, D, D, D, D, P]),
 }
 EXPORTS = tuple(_SIGNATURES)
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 
 def _bind(path: str):

@@ -13,6 +13,7 @@
 #include "kernels/gemm8.h"
 #include "kernels/gemm9.h"
 #include "kernels/gemm_small.h"
+#include "kernels/optim.h"
 #ifdef XCLIP_MEASURE                                             // negative-result experiments, measurement build only (DESIGN_APPENDIX.md 6b)
 #include "kernels/measure/gemm6.h"
 #include "kernels/measure/gemm7.h"
@@ -1631,6 +1632,57 @@ int xclip_neg_cosine_bwd(const void* p, const void* z, const float* cosv, const 
         hipLaunchKernelGGL((neg_cosine_bwd_kernel<bf16_t>), grid, block, 0, (hipStream_t)stream, (const bf16_t*)p, (const bf16_t*)z, cosv, rp, rz, gmul, coef, (bf16_t*)dp, (int)rows, (int)dim);
     else
         hipLaunchKernelGGL((neg_cosine_bwd_kernel<float>), grid, block, 0, (hipStream_t)stream, (const float*)p, (const float*)z, cosv, rp, rz, gmul, coef, (float*)dp, (int)rows, (int)dim);
+    return check_launch(__func__);
+}
+
+// ---- the optimizer step (kernels/optim.h) ---------------------------------------------------------------------------------------------
+int xclip_gradnorm_partial(const void* table, int64_t chunk0, int64_t count, int g_dtype, float* partials, void* stream) {
+    XC_REQUIRE(dtype_ok(g_dtype), "bad gradient dtype");
+    XC_REQUIRE(chunk0 >= 0 && count >= 0 && chunk0 + count < (1ll << 31), "bad chunk range");
+    if (count == 0) return 0;
+    XC_REQUIRE(table && partials && aligned16(table), "null or misaligned pointer");
+    dim3 grid((unsigned)count), block(OPT_THREADS);
+    if (g_dtype == XCLIP_BF16)
+        hipLaunchKernelGGL((gradnorm_partial_kernel<bf16_t>), grid, block, 16, (hipStream_t)stream, (const OptChunk*)table, (int)chunk0, partials);
+    else
+        hipLaunchKernelGGL((gradnorm_partial_kernel<float>), grid, block, 16, (hipStream_t)stream, (const OptChunk*)table, (int)chunk0, partials);
+    return check_launch(__func__);
+}
+
+int xclip_optim_prepare(const float* partials, int64_t n_chunks, float max_norm, int clip, void* state_block, int32_t* step_base,
+                        const int32_t* absent, int64_t n_absent, void* stream) {
+    XC_REQUIRE(n_chunks > 0 && n_chunks < (1ll << 31) && n_absent >= 0 && n_absent < (1ll << 31), "bad counts");
+    XC_REQUIRE(partials && state_block && step_base && (n_absent == 0 || absent), "null pointer");
+    XC_REQUIRE(!clip || (max_norm > 0.f && max_norm == max_norm), "max_norm must be positive");
+    static_assert(sizeof(OptBlock) == 32 && sizeof(OptChunk) == 48, "x_clip_amd/optim.py builds these layouts");
+    hipLaunchKernelGGL(optim_prepare_kernel, dim3(1), dim3(OPT_THREADS), OPT_THREADS * 8, (hipStream_t)stream, partials, (int)n_chunks, max_norm,
+                       clip ? 1 : 0, (OptBlock*)state_block, step_base, absent, (int)n_absent);
+    return check_launch(__func__);
+}
+
+int xclip_adamw_step(const void* table, int64_t chunk0, int64_t count, int p_dtype, int g_dtype, float* exp_avg, float* exp_avg_sq,
+                     float* master, const void* state_block, int32_t* step_base, double lr, double beta1, double beta2, double eps,
+                     double weight_decay, void* stream) {
+    XC_REQUIRE(dtype_ok(p_dtype) && dtype_ok(g_dtype), "bad dtype");
+    XC_REQUIRE(chunk0 >= 0 && count >= 0 && chunk0 + count < (1ll << 31), "bad chunk range");
+    XC_REQUIRE(lr >= 0.0 && lr < 1e30 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0 && eps < 1e30 &&
+               weight_decay >= 0.0 && weight_decay < 1e30, "bad hyper-parameter");
+    if (count == 0) return 0;
+    XC_REQUIRE(table && exp_avg && exp_avg_sq && state_block && step_base && aligned16(table) && aligned16(exp_avg) && aligned16(exp_avg_sq),
+               "null or misaligned pointer");
+    XC_REQUIRE(p_dtype == XCLIP_F32 || (master && aligned16(master)), "bf16 parameters need the fp32 master array");
+    AdamWArgs a;
+    a.decay = (float)(1.0 - lr * weight_decay);
+    a.b1 = (float)beta1; a.omb1 = (float)(1.0 - beta1);
+    a.b2 = (float)beta2; a.omb2 = (float)(1.0 - beta2);
+    a.eps = (float)eps;
+    a.lr = lr; a.beta1 = beta1; a.beta2 = beta2;
+    dim3 grid((unsigned)count), block(OPT_THREADS);
+    hipStream_t st = (hipStream_t)stream;
+#define XC_ADAMW(P, G, M) hipLaunchKernelGGL((adamw_kernel<P, G, M>), grid, block, 0, st, (const OptChunk*)table, (int)chunk0, exp_avg, exp_avg_sq, master, (const OptBlock*)state_block, step_base, a)
+    if (p_dtype == XCLIP_BF16) { if (g_dtype == XCLIP_BF16) XC_ADAMW(bf16_t, bf16_t, true); else XC_ADAMW(bf16_t, float, true); }
+    else                       { if (g_dtype == XCLIP_BF16) XC_ADAMW(float, bf16_t, false); else XC_ADAMW(float, float, false); }
+#undef XC_ADAMW
     return check_launch(__func__);
 }
 

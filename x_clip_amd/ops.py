@@ -1110,3 +1110,40 @@ def ntxent_lse(q: Tensor, other: Tensor, scale: float, coef: float, loss_accum: 
                "xclip_simloss_partial")
     _lib.check(L.xclip_simloss_combine(ws.data_ptr(), nq, slots, pos.data_ptr(), lse.data_ptr(), _ptr(loss_accum), coef, st), "xclip_simloss_combine")
     return lse
+
+
+# ---- the optimizer step (x_clip_amd/optim.py) --------------------------------------------------------------------------------------
+OPTIM_CHUNK = 65536            # elements per chunk-table record at most (csrc/kernels/optim.h OPT_CHUNK)
+OPTIM_CHUNK_BYTES = 48         # sizeof(OptChunk)
+OPTIM_BLOCK_WORDS = 8          # sizeof(OptBlock) / 4: grad_norm, clip_coef (fp32), found_nonfinite, step, skipped (int32), 3 reserved
+
+
+def gradnorm_partial(table: Tensor, chunk0: int, count: int, grad_dtype, partials: Tensor) -> None:
+    """partials[c] = sum of squares of the gradient piece chunk record c names, c in [chunk0, chunk0 + count) (all of `grad_dtype`)"""
+    _dev_check(table, partials)
+    assert table.dtype == torch.uint8 and table.numel() >= (chunk0 + count) * OPTIM_CHUNK_BYTES
+    assert partials.dtype == torch.float32 and partials.numel() >= chunk0 + count
+    _lib.check(_lib.lib().xclip_gradnorm_partial(table.data_ptr(), chunk0, count, _DTYPES[grad_dtype], partials.data_ptr(), _stream(table)),
+               "xclip_gradnorm_partial")
+
+
+def optim_prepare(partials: Tensor, n_chunks: int, max_norm: Optional[float], block: Tensor, step_base: Tensor, absent: Optional[Tensor],
+                  n_absent: int) -> None:
+    """partials -> the device state block (norm, clip factor, non-finite flag, step / skipped counters); no host read"""
+    _dev_check(partials, block, step_base, absent)
+    assert block.dtype == torch.int32 and block.numel() == OPTIM_BLOCK_WORDS and step_base.dtype == torch.int32
+    assert partials.numel() >= n_chunks and (n_absent == 0 or (absent.dtype == torch.int32 and absent.numel() >= n_absent))
+    _lib.check(_lib.lib().xclip_optim_prepare(partials.data_ptr(), n_chunks, 0.0 if max_norm is None else float(max_norm), int(max_norm is not None),
+                                              block.data_ptr(), step_base.data_ptr(), _ptr(absent) if n_absent else 0, n_absent, _stream(block)),
+               "xclip_optim_prepare")
+
+
+def adamw_step(table: Tensor, chunk0: int, count: int, param_dtype, grad_dtype, exp_avg: Tensor, exp_avg_sq: Tensor, master: Optional[Tensor],
+               block: Tensor, step_base: Tensor, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float) -> None:
+    """one param group's chunks [chunk0, chunk0 + count) of one (parameter dtype, gradient dtype): the fused AdamW update"""
+    _dev_check(table, exp_avg, exp_avg_sq, master, block, step_base)
+    assert table.dtype == torch.uint8 and table.numel() >= (chunk0 + count) * OPTIM_CHUNK_BYTES
+    assert exp_avg.dtype == torch.float32 and exp_avg_sq.dtype == torch.float32 and (master is None or master.dtype == torch.float32)
+    _lib.check(_lib.lib().xclip_adamw_step(table.data_ptr(), chunk0, count, _DTYPES[param_dtype], _DTYPES[grad_dtype], exp_avg.data_ptr(),
+                                           exp_avg_sq.data_ptr(), _ptr(master), block.data_ptr(), step_base.data_ptr(), float(lr), float(beta1),
+                                           float(beta2), float(eps), float(weight_decay), _stream(table)), "xclip_adamw_step")

@@ -1,0 +1,334 @@
+"""The step after `loss.backward()`: clip-by-global-norm + AdamW as three kinds of kernel launches over ALL parameters (csrc/kernels/optim.h),
+with fp32 master weights for bf16 parameters kept inside the optimizer.
+
+    opt = FusedAdamW(FusedAdamW.default_param_groups(model, weight_decay=0.2), lr=5e-4, max_grad_norm=1.0)
+    loss.backward(); sync.finish(); opt.step(); opt.zero_grad()
+
+Why: `torch.optim.AdamW` on a `.bfloat16()` model keeps both moments in bf16 and adds lr * update to an 8-bit mantissa -- at CLIP's
+learning rates most updates are below half an ulp of the weight and are rounded away.  Here the model keeps exactly the bf16 tensors it
+has (forward and backward are untouched); the optimizer owns an fp32 copy, updates that, and writes each parameter as its rounded value.
+Python does bookkeeping only: every number is computed by the HIP kernels, nothing is read back to the host during a step.
+"""
+from __future__ import annotations
+
+from itertools import chain
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import ops
+
+_ALIGN_ELEMS = 32                                               # state slices are 128-byte aligned (as GradSync's)
+# csrc/kernels/optim.h OptChunk
+_TABLE_DTYPE = np.dtype([("p", "<u8"), ("g", "<u8"), ("state_off", "<i8"), ("n", "<i4"), ("dtypes", "<i4"), ("param", "<i4"),
+                         ("first", "<i4"), ("reserved", "<i4", (2,))])
+assert _TABLE_DTYPE.itemsize == ops.OPTIM_CHUNK_BYTES
+_CODE = {torch.float32: 0, torch.bfloat16: 1}
+_STAGING = 4                                                    # pinned staging buffers per device (see _DeviceState)
+_GROUP_KEYS = ("lr", "betas", "eps", "weight_decay")           # what a param group means here
+_BLK_NORM, _BLK_CLIP, _BLK_BAD, _BLK_STEP, _BLK_SKIPPED = 0, 1, 2, 3, 4
+
+
+class _DeviceState:
+    """flat state, chunk table and state block of the parameters that live on one device"""
+
+    def __init__(self, device, params):
+        self.device = device
+        # bf16 parameters first: the master array covers only them
+        self.params = [pg for pg in params if pg[0].dtype == torch.bfloat16] + [pg for pg in params if pg[0].dtype != torch.bfloat16]
+        self.offset, off, master_len = [], 0, 0
+        for p, _ in self.params:
+            self.offset.append(off)
+            off += (p.numel() + _ALIGN_ELEMS - 1) // _ALIGN_ELEMS * _ALIGN_ELEMS
+            if p.dtype == torch.bfloat16:
+                master_len = off
+        self.exp_avg = torch.zeros(max(off, 1), dtype=torch.float32, device=device)
+        self.exp_avg_sq = torch.zeros(max(off, 1), dtype=torch.float32, device=device)
+        self.master = torch.zeros(master_len, dtype=torch.float32, device=device) if master_len else None
+        self.block = torch.zeros(ops.OPTIM_BLOCK_WORDS, dtype=torch.int32, device=device)
+        self.step_base = torch.full((max(len(self.params), 1),), -1, dtype=torch.int32, device=device)
+        self.max_chunks = sum((p.numel() + ops.OPTIM_CHUNK - 1) // ops.OPTIM_CHUNK for p, _ in self.params)
+        table_bytes = max(self.max_chunks, 1) * ops.OPTIM_CHUNK_BYTES
+        # one buffer = the chunk table followed by the list of parameters without a gradient: one copy per rebuild
+        self.upload = torch.zeros(table_bytes + 4 * max(len(self.params), 1), dtype=torch.uint8, device=device)
+        self.table = self.upload[:table_bytes]
+        self.absent = self.upload[table_bytes:].view(torch.int32)
+        # a ring of pinned staging buffers, each with the event behind its last asynchronous copy: a rebuild waits on the host only if
+        # the copy issued _STAGING rebuilds ago has not left its buffer yet (the host that far ahead of the device)
+        self.staging = [torch.zeros(self.upload.numel(), dtype=torch.uint8, pin_memory=device.type == "cuda") for _ in range(_STAGING)]
+        self.staged = [None] * _STAGING
+        self.rebuilds = 0
+        self.partials = torch.zeros(max(self.max_chunks, 1), dtype=torch.float32, device=device)
+        self.signature = None
+        self.n_chunks = self.n_absent = 0
+        self.segments = []                                      # (first chunk, chunks, param group, parameter dtype, gradient dtype)
+        self.norm_segments = []                                 # (first chunk, chunks, gradient dtype)
+
+    def view(self, flat, i):
+        p = self.params[i][0]
+        return flat[self.offset[i]: self.offset[i] + p.numel()].view(p.shape)
+
+
+class FusedAdamW(torch.optim.Optimizer):
+    """AdamW (decoupled weight decay, `torch.optim.AdamW`'s formula and operation order) with optional clipping by the global gradient
+    norm (`torch.nn.utils.clip_grad_norm_`'s formula), fused into HIP kernels that walk every parameter through a chunk table in device
+    memory.  float32 and bfloat16 parameters; gradients float32 or bfloat16, wherever autograd or `GradSync.claim` put them.
+
+    * bf16 parameters get an fp32 MASTER copy (initialised from the parameter: exact); the update is applied to the master and the parameter
+      is written as its round-to-nearest-even bf16.  The moments are fp32 for every parameter.  fp32 parameters have no master.
+    * `max_grad_norm`: gradients are scaled by min(1, max_grad_norm / (norm + 1e-6)) inside the update (`.grad` itself is NOT modified).
+      The norm pass always runs: a non-finite norm (an inf / nan gradient anywhere) SKIPS the step on the device -- parameters, moments,
+      masters and step counts stay bit-identical, `skipped_steps` goes up by one.
+    * no host synchronisation: the norm, the clip factor, the skip decision and the step counts live in device memory.  `grad_norm`,
+      `skipped_steps` and `step_count` are device tensors (views of that state); reading them is the caller's choice to pay for a sync.
+    * hyper-parameters are kernel arguments read from `param_groups` at every step: LR schedulers work, nothing is uploaded for them.
+    * the chunk table is rebuilt and uploaded (pinned staging buffer, asynchronous copy) only when a parameter's or gradient's address, or
+      the set of parameters that have a gradient, differs from the previous step (`table_uploads` counts).  With `GradSync` the gradients
+      are persistent slices: from the second step on nothing is uploaded.  Plain autograd with `zero_grad(set_to_none=True)` may hand
+      out fresh gradient addresses every step: then every step rebuilds (host time) and uploads, through a ring of 4 pinned staging
+      buffers -- the host waits only if it runs more than 4 rebuilt steps ahead of the device: that bounds the queue, it does not drain it.
+    * parameters whose `.grad` is None are left alone and their own step count does not advance (torch semantics).
+
+    Streams: `step()` runs on the current stream.  The backward's side streams join the current stream before `backward()` returns; with
+    `GradSync` call `sync.finish()` FIRST (it orders the current stream behind the all-reduces).  Distributed training needs nothing else:
+    after `finish()` every rank holds the same averaged gradients, so the norm, the clip factor and the skip decision are identical on
+    every rank without a collective.  All parameters of one norm live on one device: with parameters on several devices each device
+    clips by (and skips on) the norm of its own parameters.
+
+    `zero_grad()` (set_to_none=True, torch's default) is what `GradSync` wants: its weight-gradient kernels write straight into the
+    persistent slice only while `.grad` is None, and the re-created `.grad` has the same address, so the table stays valid."""
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
+                 max_grad_norm: Optional[float] = None):
+        if not 0.0 <= lr:
+            raise ValueError(f"invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"invalid eps: {eps}")
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"invalid betas: {betas}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"invalid weight_decay: {weight_decay}")
+        if max_grad_norm is not None and not max_grad_norm > 0.0:
+            raise ValueError(f"invalid max_grad_norm: {max_grad_norm}")
+        self._devs = None
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self.max_grad_norm = max_grad_norm
+        self.table_uploads = 0                                  # chunk-table uploads so far (tests: none from the second GradSync step on)
+        self._build()
+
+    # ---- state ----
+    def add_param_group(self, param_group):
+        if self._devs is not None:
+            raise NotImplementedError("x_clip_amd FusedAdamW: parameter groups are fixed at construction (the flat state is laid out once)")
+        super().add_param_group(param_group)
+
+    def _build(self):
+        by_dev = {}
+        for gi, group in enumerate(self.param_groups):
+            for p in group["params"]:
+                if p.dtype not in _CODE:
+                    raise TypeError(f"x_clip_amd FusedAdamW supports float32 and bfloat16 parameters, got {p.dtype}")
+                if not p.is_contiguous():
+                    raise RuntimeError("x_clip_amd FusedAdamW: parameters must be contiguous")
+                ops._dev_check(p)
+                if p.numel():
+                    by_dev.setdefault(p.device, []).append((p, gi))
+        self._devs = {dev: _DeviceState(dev, ps) for dev, ps in by_dev.items()}
+        self._where = {}                                        # id(param) -> (device state, index)
+        with torch.no_grad():
+            for D in self._devs.values():
+                for i, (p, _) in enumerate(D.params):
+                    self._where[id(p)] = (D, i)
+                    st = self.state[p]
+                    st["exp_avg"], st["exp_avg_sq"] = D.view(D.exp_avg, i), D.view(D.exp_avg_sq, i)
+                    if p.dtype == torch.bfloat16:
+                        st["master"] = D.view(D.master, i)
+                        st["master"].copy_(p)                   # bf16 -> fp32: exact
+
+    def _one(self) -> _DeviceState:
+        if len(self._devs) != 1:
+            raise RuntimeError("x_clip_amd FusedAdamW: grad_norm / skipped_steps / step_count are per device; this optimizer holds "
+                               f"parameters on {len(self._devs)} devices")
+        return next(iter(self._devs.values()))
+
+    @property
+    def grad_norm(self) -> torch.Tensor:
+        """device scalar (fp32): the global gradient norm the last step() saw (before clipping; inf / nan when that step was skipped)"""
+        return self._one().block[_BLK_NORM: _BLK_NORM + 1].view(torch.float32)[0]
+
+    @property
+    def skipped_steps(self) -> torch.Tensor:
+        """device scalar (int32): steps skipped because a gradient was not finite"""
+        return self._one().block[_BLK_SKIPPED]
+
+    @property
+    def step_count(self) -> torch.Tensor:
+        """device scalar (int32): steps applied (skipped ones not counted)"""
+        return self._one().block[_BLK_STEP]
+
+    # ---- the chunk table ----
+    def _rebuild(self, D: _DeviceState, grads):
+        recs, absent = [], []
+        for i, ((p, gi), g) in enumerate(zip(D.params, grads)):
+            if g is None:
+                absent.append(i)
+                continue
+            if g.device != p.device:
+                raise RuntimeError(f"x_clip_amd FusedAdamW: a gradient lives on {g.device}, its parameter on {p.device}")
+            if g.is_sparse or g.dtype not in _CODE or g.shape != p.shape or not g.is_contiguous():
+                raise RuntimeError("x_clip_amd FusedAdamW: gradients must be dense, contiguous, float32 or bfloat16 and of the parameter's shape "
+                                   f"(got {g.dtype}, {tuple(g.shape)}, contiguous={g.is_contiguous()})")
+            pc, gc = _CODE[p.dtype], _CODE[g.dtype]
+            pe, ge, pp, gp = p.element_size(), g.element_size(), p.data_ptr(), g.data_ptr()
+            for k, lo in enumerate(range(0, p.numel(), ops.OPTIM_CHUNK)):
+                n = min(ops.OPTIM_CHUNK, p.numel() - lo)
+                recs.append(((gi, pc, gc), (pp + lo * pe, gp + lo * ge, D.offset[i] + lo, n, pc | (gc << 8), i, int(k == 0), (0, 0))))
+        recs.sort(key=lambda r: r[0])                           # (stable: parameters keep their order inside a segment)
+        assert len(recs) <= D.max_chunks
+        D.segments, D.norm_segments = [], []
+        for c, (key, _) in enumerate(recs):
+            if D.segments and tuple(D.segments[-1][2:]) == key:
+                D.segments[-1][1] += 1
+            else:
+                D.segments.append([c, 1, *key])
+            if D.norm_segments and D.norm_segments[-1][2] == key[2]:
+                D.norm_segments[-1][1] += 1
+            else:
+                D.norm_segments.append([c, 1, key[2]])
+        D.n_chunks, D.n_absent = len(recs), len(absent)
+        slot = D.rebuilds % _STAGING
+        D.rebuilds += 1
+        if D.staged[slot] is not None:
+            D.staged[slot].synchronize()                        # (the copy issued _STAGING rebuilds ago has left this buffer: normally long done)
+        host = D.staging[slot].numpy()
+        tb = D.table.numel()
+        if recs:
+            host[: len(recs) * ops.OPTIM_CHUNK_BYTES] = np.array([r[1] for r in recs], dtype=_TABLE_DTYPE).view(np.uint8)
+        if absent:
+            host[tb: tb + 4 * len(absent)] = np.array(absent, dtype=np.int32).view(np.uint8)
+        D.upload.copy_(D.staging[slot], non_blocking=True)
+        if D.device.type == "cuda":
+            D.staged[slot] = torch.cuda.current_stream(D.device).record_event()
+        self.table_uploads += 1
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        dt = {0: torch.float32, 1: torch.bfloat16}
+        for D in self._devs.values():
+            grads = [p.grad for p, _ in D.params]
+            # (address, dtype AND layout: a strided or reshaped gradient swapped in at the same address must reach _rebuild's checks)
+            signature = tuple((p.data_ptr(), None if g is None else (g.data_ptr(), g.dtype, g.shape == p.shape and g.is_contiguous()))
+                              for (p, _), g in zip(D.params, grads))
+            if signature != D.signature:
+                self._rebuild(D, grads)
+                D.signature = signature
+            if D.n_chunks == 0:
+                continue
+            ctx = torch.cuda.device(D.device) if D.device.type == "cuda" else _null()
+            with ctx:
+                for c0, n, gc in D.norm_segments:
+                    ops.gradnorm_partial(D.table, c0, n, dt[gc], D.partials)
+                ops.optim_prepare(D.partials, D.n_chunks, self.max_grad_norm, D.block, D.step_base, D.absent, D.n_absent)
+                for c0, n, gi, pc, gc in D.segments:
+                    g = self.param_groups[gi]
+                    ops.adamw_step(D.table, c0, n, dt[pc], dt[gc], D.exp_avg, D.exp_avg_sq, D.master, D.block, D.step_base,
+                                   g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"])
+        return loss
+
+    # ---- checkpoints ----
+    def state_dict(self):
+        """`torch.optim.AdamW`'s layout (`step`, `exp_avg`, `exp_avg_sq` per parameter that has been stepped, fp32) plus `master` for bf16
+        parameters and, beside torch's two keys, `max_grad_norm` and `skipped_steps` (per device).  Copies (not views of the flat state);
+        reads the step counts back: a checkpoint is a synchronisation point.  `register_state_dict_pre_hook` / `_post_hook` hooks run."""
+        for hook in self._optimizer_state_dict_pre_hooks.values():
+            hook(self)
+        packed, index = [], {}
+        for group in self.param_groups:
+            g = {k: v for k, v in group.items() if k != "params"}
+            g["params"] = []
+            for p in group["params"]:
+                index[id(p)] = len(index)
+                g["params"].append(index[id(p)])
+            packed.append(g)
+        state = {}
+        for D in self._devs.values():
+            total = int(D.block[_BLK_STEP])
+            base = D.step_base.tolist()
+            for i, (p, _) in enumerate(D.params):
+                if base[i] < 0:
+                    continue                                    # never stepped: no state, as in torch
+                st = {"step": torch.tensor(float(total - base[i])), "exp_avg": D.view(D.exp_avg, i).clone(),
+                      "exp_avg_sq": D.view(D.exp_avg_sq, i).clone()}
+                if p.dtype == torch.bfloat16:
+                    st["master"] = D.view(D.master, i).clone()
+                state[index[id(p)]] = st
+        out = {"state": state, "param_groups": packed, "max_grad_norm": self.max_grad_norm,
+               "skipped_steps": {str(D.device): int(D.block[_BLK_SKIPPED]) for D in self._devs.values()}}
+        for hook in self._optimizer_state_dict_post_hooks.values():
+            res = hook(self, out)
+            out = out if res is None else res
+        return out
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict):
+        """accepts state_dict() of this class and of `torch.optim.AdamW` (no `master`: the masters are initialised from the parameters).
+        Not the base class's: that one casts floating-point state to the PARAMETER's dtype, which would round the fp32 moments and masters
+        of bf16 parameters to bf16.  Of a saved param group only lr / betas / eps / weight_decay are taken (torch's foreach, fused,
+        capturable ... mean nothing here; amsgrad / maximize are refused); `skipped_steps` is restored when present;
+        `register_load_state_dict_pre_hook` / `_post_hook` hooks run."""
+        for hook in self._optimizer_load_state_dict_pre_hooks.values():
+            res = hook(self, state_dict)
+            state_dict = state_dict if res is None else res
+        saved = state_dict["param_groups"]
+        if len(saved) != len(self.param_groups) or any(len(s["params"]) != len(g["params"]) for s, g in zip(saved, self.param_groups)):
+            raise ValueError("loaded state dict has different parameter groups")
+        ids = dict(zip(chain.from_iterable(s["params"] for s in saved), chain.from_iterable(g["params"] for g in self.param_groups)))
+        if any(s.get("amsgrad") or s.get("maximize") for s in saved):
+            raise ValueError("x_clip_amd FusedAdamW has no amsgrad / maximize variant")
+        for s, g in zip(saved, self.param_groups):
+            g.update({k: s[k] for k in _GROUP_KEYS if k in s})
+        if "max_grad_norm" in state_dict:
+            self.max_grad_norm = state_dict["max_grad_norm"]
+        loaded = {id(ids[k]): v for k, v in state_dict["state"].items()}
+        for D in self._devs.values():
+            steps = [int(float(loaded[id(p)]["step"])) if id(p) in loaded else None for p, _ in D.params]
+            total = max([s for s in steps if s is not None], default=0)
+            for i, (p, _) in enumerate(D.params):
+                st = loaded.get(id(p))
+                m, v = D.view(D.exp_avg, i), D.view(D.exp_avg_sq, i)
+                if st is None:
+                    m.zero_()
+                    v.zero_()
+                else:
+                    m.copy_(st["exp_avg"])
+                    v.copy_(st["exp_avg_sq"])
+                if p.dtype == torch.bfloat16:
+                    D.view(D.master, i).copy_(st["master"] if st is not None and "master" in st else p)
+            D.step_base.copy_(torch.tensor([-1 if s is None else total - s for s in steps] or [-1], dtype=torch.int32))
+            D.block[_BLK_STEP] = total
+            D.block[_BLK_SKIPPED] = int(state_dict.get("skipped_steps", {}).get(str(D.device), 0))
+            D.signature = None
+        for hook in self._optimizer_load_state_dict_post_hooks.values():
+            hook(self)
+
+    # ---- helpers ----
+    @staticmethod
+    def default_param_groups(model: torch.nn.Module, weight_decay: float = 1e-2):
+        """two groups: weight matrices with `weight_decay`; everything with ndim < 2 (LayerNorm gains, biases, cls token, temperature) and
+        the embedding tables without"""
+        tables = {id(m.weight) for m in model.modules() if isinstance(m, torch.nn.Embedding)}
+        decay, plain = [], []
+        for p in model.parameters():
+            if p.requires_grad:
+                (plain if p.ndim < 2 or id(p) in tables else decay).append(p)
+        return [{"params": decay, "weight_decay": weight_decay}, {"params": plain, "weight_decay": 0.0}]
+
+
+class _null:
+    def __enter__(self): return None
+    def __exit__(self, *exc): return False
