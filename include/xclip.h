@@ -187,7 +187,12 @@ int xclip_ffn_dgrad_geglu_rowc(const void* dout, int64_t ldd, const void* w2, in
  * dropout_p > 0: attention dropout on the softmax probabilities (Attention.dropout, x_clip.py:212,241): probability (b, h, i, j) is kept,
  * and scaled by 1 / (1 - p), iff the 32-bit mix of (dropout_seed, ((b heads + h) n + i) n + j) is >= p 2^32 (csrc/kernels/common.h
  * drop_hash) -- the backward (and a checkpointed re-run of the forward) must be given the same seed.  Runs the tiled kernels.
- * A query with no visible key gets output 0 (the reference's softmax over all -max scores gives the uniform average there). */
+ * A query with no visible key gets output 0 (the reference's softmax over all -max scores gives the uniform average there).
+ * lse[b, h, i] = the NATURAL log of the sum over the keys query i sees of exp(scale q_i . k_j), in every kernel generation (the tiled
+ * kernels keep their running maximum in natural units of the scaled scores, the head-resident ones in log2 units of them -- they take the
+ * maximum of the raw scores first, hence scale > 0 there -- and convert on store).  Keys that are masked out, hidden by the causal mask or
+ * padding are not in the sum; dropout does not enter it (the normaliser sums the undropped probabilities).  Every generation's backward
+ * reads it under that one convention (tests: `attn lse` against log-sum-exp of the fp64 scores).  Undefined for a query with no visible key. */
 int xclip_attention_fwd(const void* qkv, const uint8_t* mask, void* out, float* lse, int64_t batch, int64_t n,
                         int64_t heads, int64_t head_dim, float scale, int causal, float dropout_p, uint64_t dropout_seed, int dtype,
                         void* stream);

@@ -65,10 +65,10 @@ def close(got, want, dtype, name="", scale=None, mult=1.0, ulps=1.0, unit="elem"
                    an output element is set by the magnitude of the terms summed into it, not by its own size, so the check is
                    max |got - bf16(want)| <= `ulps` ulps OF THE OUTPUT SCALE; each such case states its bound next to the measured
                    value (tests print both into gpurun_out/parity_report_*.txt)."""
-    got = got.detach().cpu().to(torch.float64)
-    want = want.detach().cpu().to(torch.float64)
+    want = want.detach().to(torch.float64)                      # the arithmetic runs where the REFERENCE lives: a full-size reference built on
+    got = got.detach().to(want.device, torch.float64)          # the GPU (attention_ref_blocked) is compared there, every element, nothing sampled
     assert got.shape == want.shape, (name, got.shape, want.shape)
-    s = max(float(want.abs().max()) if scale is None else scale, 1e-30)
+    s = max(float(want.abs().max()) if scale is None else scale, 1e-30)       # the scale of the WHOLE tensor
     assert bool(torch.isfinite(got).all()), name
     if dtype == torch.float32:
         err = float((got - want).abs().max())
@@ -82,11 +82,11 @@ def close(got, want, dtype, name="", scale=None, mult=1.0, ulps=1.0, unit="elem"
         label = "bf16 ulp, element-wise"
     else:
         assert unit == "scale"
-        err_ulps = float(diff.max() / bf16_ulp(torch.tensor(s, dtype=torch.float64)))
+        err_ulps = float(diff.max()) / float(bf16_ulp(torch.tensor(s, dtype=torch.float64)))
         label = "bf16 ulp of the output scale"
     _record(name, dtype, err_ulps, ulps, label)
     if os.environ.get("XCLIP_TEST_MEASURE_ONLY") == "1":
-        other = float(diff.max() / bf16_ulp(torch.tensor(s, dtype=torch.float64)))
+        other = float(diff.max()) / float(bf16_ulp(torch.tensor(s, dtype=torch.float64)))
         _record(name + " {scale-ulp}", dtype, other, 0, "info")
         return
     assert err_ulps <= ulps, f"{name}: {err_ulps:.3f} {label} (bound {ulps}) at output scale {s:.3e}"
@@ -341,7 +341,9 @@ def case_gemm(dev, dtype, M, N, K, layout, epilogue=False, alpha=1.0, residual_o
     close(c, r, dtype, f"gemm {layout} {M}x{N}x{K}", scale=max(scale, float(r.abs().max())))
 
 
-def _attention_ref(qkv64, mask, heads, scale, causal=False, hd=64, drop=None):
+def _attention_ref(qkv64, mask, heads, scale, causal=False, hd=64, drop=None, with_lse=False):
+    """with_lse: also the natural log of the sum of exponentials of the scaled scores over the keys a query sees [b, heads, n] -- what
+    xclip_attention_fwd saves for the backward (include/xclip.h): masked and hidden keys are not in the sum, dropout does not enter it"""
     b, n, _ = qkv64.shape
     q, k, v = qkv64.view(b, n, 3, heads, hd).permute(2, 0, 3, 1, 4)
     s = (q * scale) @ k.transpose(-1, -2)
@@ -352,7 +354,8 @@ def _attention_ref(qkv64, mask, heads, scale, causal=False, hd=64, drop=None):
     p = torch.softmax(s, dim=-1)
     if drop is not None:                                        # (p, seed): the product's keep-mask over (b, h, i, j), rebuilt on the host
         p = p * O.dropout_keep(drop[1], b * heads * n * n, drop[0]).view(b, heads, n, n).double() / (1.0 - float(np.float32(drop[0])))
-    return (p @ v).permute(0, 2, 1, 3).reshape(b, n, heads * hd)
+    o = (p @ v).permute(0, 2, 1, 3).reshape(b, n, heads * hd)
+    return (o, torch.logsumexp(s.detach(), dim=-1)) if with_lse else o
 
 
 def case_attention(dev, dtype, batch, n, heads, masked, causal=False, hd=64, drop=None, mask_override=None):
@@ -375,10 +378,11 @@ def case_attention(dev, dtype, batch, n, heads, masked, causal=False, hd=64, dro
     dk = {} if drop is None else dict(dropout_p=drop[0], dropout_seed=drop[1])
     out, lse = ops.attention_fwd(qkv.to(dev), None if mask is None else mask.to(dev), heads, scale, causal, hd, **dk)
     q64 = ref64(qkv).requires_grad_(True)
-    r = _attention_ref(q64, mask, heads, scale, causal, hd, drop)
+    r, lse_r = _attention_ref(q64, mask, heads, scale, causal, hd, drop, with_lse=True)
     r.backward(ref64(dout))
     tag = ("" if hd == 64 else f" (head slot {hd})") + ("" if drop is None else " + dropout")
     close(out, r, dtype, "attn out" + tag, ulps=2.0, unit="scale")
+    close(lse, lse_r, torch.float32, "attn lse" + tag + (" <- bf16" if dtype == torch.bfloat16 else ""))     # (an fp32 output for either storage type)
     dqkv = ops.attention_bwd(qkv.to(dev), None if mask is None else mask.to(dev), out, dout.to(dev), lse, heads, scale, causal, hd, **dk)
     close(dqkv, q64.grad, dtype, "attn dqkv" + tag, mult=3.0, ulps=2.0, unit="scale")
 
@@ -406,10 +410,12 @@ def case_attention_pool(dev, dtype, batch, n, heads, masked, hd=64, row=0, causa
     vis = row + 1 if causal else None
     out, lse = ops.attention_pool_fwd(q.to(dev), kv.to(dev), m_dev, heads, scale, hd, vis)
     q64 = ref64(qkv).requires_grad_(True)
-    r = _attention_ref(q64, mask, heads, scale, causal, hd, None)[:, row]
+    r, lse_r = _attention_ref(q64, mask, heads, scale, causal, hd, None, with_lse=True)
+    r = r[:, row]
     r.backward(ref64(dout))
     tag = f" pooled row {row}" + ("" if hd == 64 else f" (head slot {hd})")
     close(out, r, dtype, "attn out" + tag, ulps=2.0, unit="scale")
+    close(lse, lse_r[:, :, row], torch.float32, "attn lse" + tag + (" <- bf16" if dtype == torch.bfloat16 else ""))
     dq, dkv = ops.attention_pool_bwd(q.to(dev), kv.to(dev), m_dev, out, dout.to(dev), lse, heads, scale, hd, vis)
     g = q64.grad
     close(dq, g[:, row, :inner], dtype, "attn dq" + tag, mult=3.0, ulps=2.0, unit="scale")
@@ -442,8 +448,222 @@ def case_attention_spike(dev, dtype):
     v[0, 70, 1, :] = v[0, 5, 0, :] * 15.0            # and a smaller spike in the second tile
     scale = 64 ** -0.5
     out, lse = ops.attention_fwd(qkv.to(dev), None, heads, scale)
-    r = _attention_ref(ref64(qkv), None, heads, scale)
+    r, lse_r = _attention_ref(ref64(qkv), None, heads, scale, with_lse=True)
     close(out, r, dtype, "attn spike", ulps=2.0, unit="scale")
+    close(lse, lse_r, torch.float32, "attn lse spike" + (" <- bf16" if dtype == torch.bfloat16 else ""))
+
+
+# ---- attention at full occupancy: a reference that scales to 8192 heads, text-like masks, every head checked ----------------------------
+def dropout_keep_range(seed, start, count, p, device):
+    """oracle.clip_oracle.dropout_keep (the product's stateless keep-mask, csrc/kernels/common.h drop_hash) for the element indices
+    [start, start + count), in torch integer arithmetic on `device`: a block of the keep-mask over (b, h, i, j) without building the
+    whole of it on the host.  Everything stays inside int64: 32 x 32-bit products are formed from 16-bit halves"""
+    M = 0xFFFFFFFF
+
+    def mul32(a, c):                                           # (a c) mod 2^32 for 0 <= a, c < 2^32
+        return (((a & 0xFFFF) * c) + ((((a >> 16) * c) & M) << 16)) & M
+
+    seed &= (1 << 64) - 1
+    idx = torch.arange(start, start + count, dtype=torch.int64, device=device)
+    h = mul32(idx & M, 0x9E3779B1) ^ mul32(idx >> 32, 0xC2B2AE3D) ^ ((seed & M) ^ (((seed >> 32) * 0x85EBCA77) & M))
+    h = h ^ (h >> 16)
+    h = mul32(h, 0x7FEB352D)
+    h = h ^ (h >> 15)
+    h = mul32(h, 0x846CA68B)
+    h = h ^ (h >> 16)
+    thresh = 0 if p <= 0 else int(np.float32(p).astype(np.float64) * 4294967296.0)
+    return h >= thresh
+
+
+def attention_ref_blocked(qkv, dout, mask, heads, scale, causal=False, hd=64, drop=None, query_row=None, block=None):
+    """_attention_ref + autograd, evaluated in blocks of samples on the device of `qkv` (one score tensor of b = 1024, n = 257, 8 heads
+    is 4.3 GB in fp64): the same expression -- scaled scores, mask fill, causal fill, softmax, the product's keep-mask, P V -- in plain
+    torch fp64, the backward by autograd.  -> (out, lse, dqkv) in fp64 on that device; lse = log sum exp of the scaled scores a query
+    sees [b, heads, n].  query_row = r: only query r of every sample (the pooled kernels): out [b, heads * hd], lse [b, heads], dout
+    [b, heads * hd]; dqkv still covers every row (its q third is zero off row r)."""
+    dev = qkv.device
+    b, n, w = qkv.shape
+    assert w == 3 * heads * hd
+    nq = n if query_row is None else 1
+    if block is None:                                          # <= 512 MB per score-sized tensor, <= 2 GB for a block of qkv in fp64
+        block = max(1, min((1 << 26) // (heads * n * nq), (1 << 28) // (n * w)))
+    neg = -torch.finfo(torch.float64).max
+    out = torch.zeros(b, nq, heads * hd, dtype=torch.float64, device=dev)
+    lse = torch.zeros(b, heads, nq, dtype=torch.float64, device=dev)
+    grad = torch.zeros(b, n, w, dtype=torch.float64, device=dev)
+    hidden = None
+    if causal:
+        hidden = torch.ones(n, n, dtype=torch.bool, device=dev).triu(1)
+        if query_row is not None:
+            hidden = hidden[query_row: query_row + 1]
+    for b0 in range(0, b, block):
+        x = qkv[b0: b0 + block].detach().to(torch.float64).requires_grad_(True)
+        bb = x.shape[0]
+        q, k, v = x.view(bb, n, 3, heads, hd).permute(2, 0, 3, 1, 4)
+        if query_row is not None:
+            q = q[:, :, query_row: query_row + 1]
+        s = (q * scale) @ k.transpose(-1, -2)
+        if mask is not None:
+            s = s.masked_fill(~mask[b0: b0 + bb, None, None, :], neg)
+        if causal:
+            s = s.masked_fill(hidden, neg)
+        lse[b0: b0 + bb] = torch.logsumexp(s.detach(), dim=-1)
+        p = torch.softmax(s, dim=-1)
+        if drop is not None:
+            assert query_row is None
+            keep = dropout_keep_range(drop[1], b0 * heads * n * n, bb * heads * n * n, drop[0], dev).view(bb, heads, n, n)
+            p = p * keep.double() / (1.0 - float(np.float32(drop[0])))
+        o = (p @ v).permute(0, 2, 1, 3).reshape(bb, nq, heads * hd)
+        out[b0: b0 + bb] = o.detach()
+        o.backward(dout[b0: b0 + bb].detach().to(torch.float64).reshape(bb, nq, heads * hd))
+        grad[b0: b0 + bb] = x.grad
+        del x, q, k, v, s, p, o
+    if query_row is not None:
+        out, lse = out[:, 0], lse[:, :, 0]
+    return out, lse, grad
+
+
+def text_mask(batch, n, seed=0):
+    """key validity shaped like padded text: position 0 (the CLS slot) always valid, then a valid prefix whose length differs per sample;
+    sample 0 keeps the CLS slot alone, sample 1 every key, every fifth sample from the third on has a hole inside its prefix"""
+    mask = torch.ones(batch, n, dtype=torch.bool)
+    if n < 2:
+        return mask
+    g = torch.Generator().manual_seed(1000 + seed)
+    L = torch.randint(2, n + 1, (batch,), generator=g)
+    L[0] = 1
+    if batch > 1:
+        L[1] = n
+    if batch > 2 and n > 3:
+        L[2] = max(int(L[2]), 4)                               # (long enough for the first hole)
+    mask = torch.arange(n)[None, :] < L[:, None]
+    for bi in range(2, batch, 5):
+        if int(L[bi]) > 3:
+            mask[bi, 1 + int(torch.randint(0, int(L[bi]) - 2, (1,), generator=g))] = False
+    return mask
+
+
+def assert_every_query_sees_a_key(mask, causal=False, query_row=None):
+    """the condition of the full-size cases: no query row with all of its visible keys masked -- there the product returns 0 where the reference's
+    softmax over all-filled scores returns the uniform average (include/xclip.h; tests/test_kernels_emu.py test_edge_cases_of_the_row_kernels)"""
+    if mask is None:
+        return
+    seen = mask.cumsum(1) > 0 if causal else mask.any(1, keepdim=True)        # [b, n] / [b, 1]: query i sees a valid key among 0 .. i / among all
+    if query_row is not None and causal:
+        seen = seen[:, query_row]
+    assert bool(seen.all()), "a query row has every visible key masked"
+
+
+def _worst_heads(got, want, heads, hd, bound_abs):
+    """which (sample, head) slots of a [b, n, k * heads * hd] tensor exceed an absolute error -- the evidence a failing full-size case prints"""
+    b, n, w = got.shape
+    d = (got.to(want.device, torch.float64) - want).abs().nan_to_num(nan=float("inf")).view(b, n, w // (heads * hd), heads, hd).amax(dim=(1, 2, 4))
+    bad = (d > bound_abs).nonzero()
+    return f"{bad.shape[0]} of {b * heads} (sample, head) slots beyond the bound; first: {bad[:12].tolist()}; work-group slots (b * heads + h): {[int(r[0]) * heads + int(r[1]) for r in bad[:12]]}"
+
+
+def _randn_nonzero(shape, g, dev, dtype):
+    """standard normal values drawn on the device, none of them zero: among 4e8 draws a few dozen are exactly 0 (Box-Muller at an angle of 0
+    or pi), and a zero dO or V element would let a misplaced one cancel -- those become 1"""
+    x = torch.randn(*shape, generator=g, device=dev).to(dtype)
+    x = torch.where(x == 0, torch.ones_like(x), x)
+    assert bool((x != 0).all())
+    return x
+
+
+def case_attention_full(dev, dtype, batch, n, heads, hd=64, masked=True, causal=False, drop=None, tag="", seed=0, repeats=3):
+    """every head of a launch that fills the chip: random qkv and dO (non-zero everywhere, different in every head: a work-group that
+    read another head's image, a stale LDS image or an image still in flight cannot cancel), outputs allocated NaN-poisoned (an element
+    no work-group wrote is NaN), out / lse / dqkv against the blocked fp64 reference under the bounds of case_attention -- in ulps of the
+    scale of the WHOLE reference tensor -- and `repeats` more launches of forward and backward bit-identical (fixed summation order, no
+    atomics: held to it under contention)."""
+    from clip_cases import poisoned_empty
+    g = torch.Generator(device=dev).manual_seed(7000 + seed)
+    qkv = _randn_nonzero((batch, n, 3 * heads * hd), g, dev, dtype)
+    dout = _randn_nonzero((batch, n, heads * hd), g, dev, dtype)
+    mask = text_mask(batch, n, seed).to(dev) if masked else None
+    assert_every_query_sees_a_key(mask, causal)
+    scale = hd ** -0.5
+    dk = {} if drop is None else dict(dropout_p=drop[0], dropout_seed=drop[1])
+
+    def launch():
+        with poisoned_empty():
+            out, lse = ops.attention_fwd(qkv, mask, heads, scale, causal, hd, **dk)
+            dqkv = ops.attention_bwd(qkv, mask, out, dout, lse, heads, scale, causal, hd, **dk)
+        return out, lse, dqkv
+
+    out, lse, dqkv = launch()
+    again = [launch() for _ in range(repeats)]
+    r_out, r_lse, r_grad = attention_ref_blocked(qkv, dout, mask, heads, scale, causal, hd, drop)
+    tag = f" full size [{tag}]"
+    for got, want, dt, name, kw in ((out, r_out, dtype, "attn out", dict(ulps=2.0, unit="scale")), (lse, r_lse, torch.float32, "attn lse", {}),
+                                    (dqkv, r_grad, dtype, "attn dqkv", dict(mult=3.0, ulps=2.0, unit="scale"))):
+        try:
+            close(got, want, dt, name + tag + (" <- bf16" if dt != dtype else ""), **kw)
+        except AssertionError as e:
+            if got.dim() != 3 or got.shape[1] != n:
+                raise
+            s = float(want.abs().max())
+            bound = 2.0 * float(bf16_ulp(torch.tensor(s, dtype=torch.float64))) if dt == torch.bfloat16 else tol(dt) * kw.get("mult", 1.0) * s
+            raise AssertionError(f"{e}\n{name}: {_worst_heads(got, want, heads, hd, bound)}; first dispatch round = work-group slots below 2 x CUs") from None
+    for i, (o2, l2, d2) in enumerate(again):
+        assert torch.equal(o2, out), f"out differs between launch 0 and {i + 1}{tag}"
+        assert torch.equal(l2, lse), f"lse differs between launch 0 and {i + 1}{tag}"
+        assert torch.equal(d2, dqkv), f"dqkv differs between launch 0 and {i + 1}{tag}"
+
+
+def case_attention_pool_full(dev, dtype, batch, n, heads, hd=64, row=0, causal=False, tag="", seed=0, repeats=3):
+    """case_attention_pool with every CU busy (one wave per (sample, head), four to a work-group: 2048 work-groups at the benchmark's batch):
+    text-like mask, poisoned outputs, every row of out / lse / dq / dkv against the blocked reference, `repeats` more launches bit-identical"""
+    from clip_cases import poisoned_empty
+    g = torch.Generator(device=dev).manual_seed(7100 + seed)
+    inner = heads * hd
+    qkv = _randn_nonzero((batch, n, 3 * inner), g, dev, dtype)
+    dout = _randn_nonzero((batch, inner), g, dev, dtype)
+    mask = text_mask(batch, n, seed).to(dev)
+    assert_every_query_sees_a_key(mask, causal, row)
+    scale = hd ** -0.5
+    q = qkv[:, row, :inner].contiguous()
+    kv = qkv[:, :, inner:].contiguous()
+    vis = row + 1 if causal else None
+
+    def launch():
+        with poisoned_empty():
+            out, lse = ops.attention_pool_fwd(q, kv, mask, heads, scale, hd, vis)
+            dq, dkv = ops.attention_pool_bwd(q, kv, mask, out, dout, lse, heads, scale, hd, vis)
+        return out, lse, dq, dkv
+
+    out, lse, dq, dkv = launch()
+    again = [launch() for _ in range(repeats)]
+    r_out, r_lse, r_grad = attention_ref_blocked(qkv, dout, mask, heads, scale, causal, hd, None, query_row=row)
+    tag = f" pooled row {row} full size [{tag}]"
+    close(out, r_out, dtype, "attn out" + tag, ulps=2.0, unit="scale")
+    close(lse, r_lse, torch.float32, "attn lse" + tag + (" <- bf16" if dtype == torch.bfloat16 else ""))
+    close(dq, r_grad[:, row, :inner], dtype, "attn dq" + tag, mult=3.0, ulps=2.0, unit="scale")
+    close(dkv, r_grad[:, :, inner:], dtype, "attn dkv" + tag, mult=3.0, ulps=2.0, unit="scale")
+    off = r_grad[:, :, :inner].clone()
+    off[:, row] = 0
+    assert float(off.abs().max()) == 0.0                       # (the reference's dQ is zero off the pooled row)
+    for i, (o2, l2, q2, k2) in enumerate(again):
+        assert torch.equal(o2, out) and torch.equal(l2, lse), f"pooled forward differs between launch 0 and {i + 1}{tag}"
+        assert torch.equal(q2, dq) and torch.equal(k2, dkv), f"pooled backward differs between launch 0 and {i + 1}{tag}"
+
+
+def case_attention_random(dev, cases, seed, max_n=400, max_batch=5, max_heads=3):
+    """a seeded sweep over what the fixed lists do not cross: storage type, head-slot width, dropout, key padding, causal masking, n from
+    1 (legal in the reference) to beyond A3_MAX_N, batch 1 .. 5 -- every dispatch branch of xclip_attention_fwd / _bwd at lengths nobody chose"""
+    g = torch.Generator().manual_seed(seed)
+
+    def ri(lo, hi):
+        return int(torch.randint(lo, hi + 1, (1,), generator=g))
+
+    for _ in range(cases):
+        dtype = DTYPES[ri(0, 1)]
+        hd = (64, 128)[ri(0, 1)]
+        drop = (0.25, 0xC0FFEE1234567 + ri(0, 1 << 20)) if ri(0, 3) == 0 else None
+        n, batch, heads = ri(1, max_n), ri(1, max_batch), ri(1, max_heads)
+        masked, causal = bool(ri(0, 1)), ri(0, 2) == 0
+        case_attention(dev, dtype, batch, n, heads, masked, causal=causal, hd=hd, drop=drop)
 
 
 def case_simloss(dev, dtype, nq, nk, d, dcl, diag_off=0, tau=1.3):

@@ -132,6 +132,98 @@ def test_attention_rescale_spike():
     K.case_attention_spike(DEV, torch.float32)
 
 
+@pytest.mark.parametrize("hd", [64, 128], ids=["hd64", "hd128"])
+@pytest.mark.parametrize("masked", [False, True], ids=["nomask", "masked"])
+@pytest.mark.parametrize("n", [289, 320, 577])
+def test_attention_bf16_above_head_resident_limit_not_causal(n, masked, hd):
+    """bf16 above A3_MAX_N = 288, NOT causal: attention2.h (64-wide heads) / attention.h on two halves with the delta pass (128-wide) --
+    n = 289 is the first length they take, 577 the ViT-L/14 at 336 token count; two samples (the second one padded), one head"""
+    K.case_attention(DEV, torch.bfloat16, 2, n, 1, masked, hd=hd)
+
+
+@pytest.mark.parametrize("hd", [64, 128], ids=["hd64", "hd128"])
+def test_attention_bf16_dropout_above_head_resident_limit(hd):
+    K.case_attention(DEV, torch.bfloat16, 2, 320, 1, True, hd=hd, drop=(0.25, 0xC0FFEE1234567))
+
+
+@pytest.mark.parametrize("dtype", K.DTYPES, ids=["fp32", "bf16"])
+@pytest.mark.parametrize("hd", [64, 128], ids=["hd64", "hd128"])
+@pytest.mark.parametrize("n", [1, 2, 5, 17, 31])
+def test_attention_shorter_than_one_block(dtype, hd, n):
+    """n < 32: one partly filled 32-row block (n = 1 is legal in the reference: a softmax over one key); plain, and for n > 3 with key
+    padding + a hole, causal, and both"""
+    K.case_attention(DEV, dtype, 2, n, 2, False, hd=hd)
+    if n > 3:
+        K.case_attention(DEV, dtype, 2, n, 2, True, hd=hd)
+        K.case_attention(DEV, dtype, 2, n, 2, False, causal=True, hd=hd)
+        K.case_attention(DEV, dtype, 2, n, 2, True, causal=True, hd=hd)
+
+
+def test_attention_random_shapes_types_widths_dropout():
+    """the GPU suite's second random sweep (storage type, head-slot width, dropout, masks, n from 1) at emulator sizes: n <= 130, one or two heads"""
+    K.case_attention_random(DEV, 10, seed=11, max_n=130, max_batch=2, max_heads=2)
+
+
+def test_blocked_attention_reference_is_the_cpu_reference():
+    """kernel_cases.attention_ref_blocked (the full-size GPU cases' reference: blocks of samples, on the device) against _attention_ref +
+    autograd on one small masked case, several blocks: out, lse and the gradient to 1e-11 of each tensor's largest magnitude.  Both are
+    fp64 sums of at most a few hundred terms: the true difference is near 1e-13, the bar leaves two orders for the summation order.
+    Also causal, with the keep-mask (rebuilt block-wise in torch integers: the same bits as the oracle's numpy form), and the one-query form"""
+    from oracle import clip_oracle as O
+    assert torch.equal(K.dropout_keep_range(0xC0FFEE1234567, 0, 5000, 0.25, DEV), O.dropout_keep(0xC0FFEE1234567, 5000, 0.25))
+    assert torch.equal(K.dropout_keep_range(0xFEDCBA9876543210, 123457, 5000, 0.3, DEV), O.dropout_keep(0xFEDCBA9876543210, 128457, 0.3)[123457:])
+
+    b, n, heads, hd = 5, 70, 3, 64
+    qkv = K.rnd((b, n, 3 * heads * hd), torch.bfloat16, 201)
+    dout = K.rnd((b, n, heads * hd), torch.bfloat16, 202)
+    mask = K.text_mask(b, n, 3)
+    K.assert_every_query_sees_a_key(mask, True)
+    assert int(mask[0].sum()) == 1 and bool(mask[1].all()) and not bool(mask[2, : int(mask[2].nonzero().max())].all())   # CLS alone, all keys, a hole
+    for causal, drop in ((False, None), (True, None), (False, (0.25, 0xC0FFEE1234567))):
+        x = K.ref64(qkv).requires_grad_(True)
+        o, l = K._attention_ref(x, mask, heads, hd ** -0.5, causal, hd, drop, with_lse=True)
+        o.backward(K.ref64(dout))
+        bo, bl, bg = K.attention_ref_blocked(qkv, dout, mask, heads, hd ** -0.5, causal, hd, drop, block=2)
+        for got, ref in ((bo, o.detach()), (bl, l), (bg, x.grad)):
+            assert got.shape == ref.shape and float((got - ref).abs().max()) <= 1e-11 * float(ref.abs().max())
+        if drop is None:
+            row = 9
+            po, pl, pg = K.attention_ref_blocked(qkv, dout[:, row], mask, heads, hd ** -0.5, causal, hd, None, query_row=row, block=2)
+            x = K.ref64(qkv).requires_grad_(True)
+            o, l = K._attention_ref(x, mask, heads, hd ** -0.5, causal, hd, None, with_lse=True)
+            o[:, row].backward(K.ref64(dout[:, row]))
+            for got, ref in ((po, o[:, row].detach()), (pl, l[:, :, row]), (pg, x.grad)):
+                assert got.shape == ref.shape and float((got - ref).abs().max()) <= 1e-11 * float(ref.abs().max())
+
+
+@pytest.mark.parametrize("dtype", K.DTYPES, ids=["fp32", "bf16"])
+def test_comparator_rejects_one_bad_element_in_the_last_head(dtype):
+    """kernel_cases.close as the full-size attention cases call it (unit="scale", 2 ulps; mult = 3 for fp32 gradients): a copy of the
+    reference with ONE element of the last head of the last sample off by 4 ulps of the tensor's scale (fp32: 4 x the bar) is rejected,
+    the reference itself accepted.  A comparison that samples, or that measures in ulps of a block's own scale, fails this: the element
+    sits where a sample would not look, in a sample 1000 x smaller than the first"""
+    saved = dict(K.REPORT)
+    try:
+        b, n, heads, hd = 6, 40, 4, 64
+        want = K.rnd((b, n, heads * hd), torch.float32, 301).double()
+        want[-1] *= 1e-3                                          # the last sample's own scale is far below the tensor's
+        s = float(want.abs().max())
+        good = want.to(dtype)
+        kw = dict(mult=3.0, ulps=2.0, unit="scale")
+        K.close(good, want, dtype, "comparator self-test", **kw)
+        step = 4.0 * (float(K.bf16_ulp(torch.tensor(s, dtype=torch.float64))) if dtype == torch.bfloat16 else K.tol(dtype) * 3.0 * s)
+        bad = good.double()
+        bad[-1, n - 1, -1] += step
+        with pytest.raises(AssertionError, match="comparator self-test"):
+            K.close(bad, want, dtype, "comparator self-test", **kw)
+        bad[-1, n - 1, -1] = float("nan")                          # and an element nobody wrote
+        with pytest.raises(AssertionError):
+            K.close(bad, want, dtype, "comparator self-test", **kw)
+    finally:
+        K.REPORT.clear()
+        K.REPORT.update(saved)
+
+
 @pytest.mark.parametrize("dtype", K.DTYPES, ids=["fp32", "bf16"])
 @pytest.mark.parametrize("dcl", [False, True])
 def test_simloss(dtype, dcl):

@@ -432,6 +432,40 @@ def test_attention_random_lengths_bf16():
         K.case_attention(DEV, torch.bfloat16, 2, n, heads, masked, causal=causal)
 
 
+def test_attention_random_shapes_types_widths_dropout():
+    """a second seeded sweep next to the one above: storage type, head-slot width (64 / 128), dropout on or off, n from 1 to 400 (both
+    sides of A3_MAX_N = 288), batch 1 .. 5 -- every branch of the dispatch at lengths nobody chose; out, lse and dqkv each time"""
+    K.case_attention_random(DEV, 24, seed=11)
+
+
+@pytest.mark.parametrize("hd", [64, 128], ids=["hd64", "hd128"])
+@pytest.mark.parametrize("masked", [False, True], ids=["nomask", "masked"])
+@pytest.mark.parametrize("n", [289, 320, 577])
+def test_attention_bf16_above_head_resident_limit_not_causal(n, masked, hd):
+    """bf16 above A3_MAX_N = 288, NOT causal: the tiled attention2.h kernels (64-wide heads) / attention.h on two halves with the delta pass
+    (128-wide) -- n = 289 is the first length they take, 577 the ViT-L/14 at 336 token count"""
+    K.case_attention(DEV, torch.bfloat16, 3, n, 3, masked, hd=hd)
+
+
+@pytest.mark.parametrize("hd", [64, 128], ids=["hd64", "hd128"])
+@pytest.mark.parametrize("masked", [False, True], ids=["nomask", "masked"])
+def test_attention_bf16_dropout_above_head_resident_limit(masked, hd):
+    K.case_attention(DEV, torch.bfloat16, 3, 320, 2, masked, hd=hd, drop=(0.25, 0xC0FFEE1234567))
+
+
+@pytest.mark.parametrize("dtype", K.DTYPES, ids=IDS)
+@pytest.mark.parametrize("hd", [64, 128], ids=["hd64", "hd128"])
+@pytest.mark.parametrize("n", [1, 2, 5, 17, 31])
+def test_attention_shorter_than_one_block(dtype, hd, n):
+    """n < 32: one partly filled 32-row block (n = 1 is legal in the reference: a softmax over one key); plain, and for n > 3 with key
+    padding + a hole, causal, and both"""
+    K.case_attention(DEV, dtype, 3, n, 2, False, hd=hd)
+    if n > 3:
+        K.case_attention(DEV, dtype, 3, n, 2, True, hd=hd)
+        K.case_attention(DEV, dtype, 3, n, 2, False, causal=True, hd=hd)
+        K.case_attention(DEV, dtype, 3, n, 2, True, causal=True, hd=hd)
+
+
 @pytest.mark.parametrize("layout,M,N,K_", [("nt", 520, 4096, 128), ("nn", 264, 3072, 64), ("nt", 256, 6144, 64)])
 def test_gemm_banded_tile_order(layout, M, N, K_):
     """more than 8 N tiles: the ring kernel's banded tile order (bands of 8 / 6 / 8 tiles) visits every tile exactly once"""
