@@ -20,7 +20,7 @@ extern "C" {
 #endif
 
 enum { XCLIP_F32 = 0, XCLIP_BF16 = 1 };
-#define XCLIP_ABI_VERSION 24
+#define XCLIP_ABI_VERSION 25
 
 int xclip_abi_version(void);
 const char* xclip_last_error(void);
@@ -243,6 +243,27 @@ int xclip_simloss_fwd(const void* Q, const void* K, int64_t nq, int64_t nk, int6
 int xclip_simloss_grad(const void* Q, const void* K, int64_t nq, int64_t nk, int64_t d, float scale, const float* log_scale,
                        int64_t diag_off, int dcl, float a, float c, float e, const float* gmul, int g_times_scale,
                        const float* lse_q, const float* lse_k, void* G, int64_t ldg, float* dtau_accum, int dtype, void* stream);
+
+/* ---- in-batch retrieval metrics of the contrastive head (the logits of x_clip.py:813-847, never stored) -----------------------
+ * Same S, Q, K, scale, log_scale and diag_off conventions as xclip_simloss_partial; col0 is the chunk's first global column.  Per row i
+ * and 64-column slot, `partial` writes cnt = #{j != i + diag_off : S_ij > thr[i]} (strict), hmax = max_j S_ij over the same columns
+ * (-3e38 if there are none) and harg = col0 + arg max (the lowest column among equal maxima) into slots [tile_slot0, tile_slot0 +
+ * ceil(nk/64)) of a workspace holding 3 * tile_slots * nq 4-byte values (xclip_simrank_workspace_bytes for one chunk).  S_ij is formed
+ * exactly as xclip_simloss_partial forms pos, so thr = that pos gives the rank of the positive (0 = it beats every negative).
+ * `pos` (x_clip.py:813-847's positives alone): thr[i] = <Q_i, K_{i+diag_off}> * scale * exp(*log_scale) for the rows whose positive lies
+ * in this chunk; other rows are left untouched.  `combine` folds all slots: rank = sum cnt, hard_val = max hmax, hard_idx = its column
+ * (lowest among equal maxima; -1 if the row has no negative).  Deterministic: no atomics anywhere. */
+int64_t xclip_simrank_workspace_bytes(int64_t nq, int64_t nk);
+/* x_clip.py:813-847 */
+int xclip_simrank_pos(const void* Q, const void* K, int64_t nq, int64_t nk, int64_t d, float scale, const float* log_scale,
+                      int64_t diag_off, float* thr, int dtype, void* stream);
+/* x_clip.py:813-847 */
+int xclip_simrank_partial(const void* Q, const void* K, int64_t nq, int64_t nk, int64_t d, float scale, const float* log_scale,
+                          int64_t diag_off, int64_t col0, const float* thr, void* workspace, int64_t tile_slot0, int64_t tile_slots,
+                          int dtype, void* stream);
+/* x_clip.py:813-847 */
+int xclip_simrank_combine(const void* workspace, int64_t nq, int64_t tile_slots, int32_t* rank, float* hard_val, int32_t* hard_idx,
+                          void* stream);
 
 /* ---- fine-grained (FILIP) head, use_all_token_embeds (x_clip.py:797-811) ----------------------------------------------------
  * The token similarity blocks come from xclip_gemm in chunks of `yc` images: S[(x, t), (y, k)] = <T[x,t], I[y0+y,k]> (no

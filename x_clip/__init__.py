@@ -13,13 +13,14 @@ of a site-packages install of the reference on `sys.path` (or do not install the
 import sys as _sys
 
 import x_clip_amd as _impl
-from x_clip_amd import distributed as _distributed, mlm as _mlm, tokenizer as _tokenizer, visual_ssl as _visual_ssl
+from x_clip_amd import distributed as _distributed, metrics as _metrics, mlm as _mlm, tokenizer as _tokenizer, visual_ssl as _visual_ssl
 
 for _name in getattr(_impl, "__all__", [n for n in dir(_impl) if not n.startswith("_")]):
     globals()[_name] = getattr(_impl, _name)
 
 _sys.modules[__name__ + ".distributed"] = _distributed
+_sys.modules[__name__ + ".metrics"] = _metrics
 _sys.modules[__name__ + ".mlm"] = _mlm
 _sys.modules[__name__ + ".visual_ssl"] = _visual_ssl
 _sys.modules[__name__ + ".tokenizer"] = _tokenizer
-distributed, mlm, visual_ssl, tokenizer = _distributed, _mlm, _visual_ssl, _tokenizer
+distributed, metrics, mlm, visual_ssl, tokenizer = _distributed, _metrics, _mlm, _visual_ssl, _tokenizer

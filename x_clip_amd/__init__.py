@@ -5,6 +5,7 @@
 Python host code (this package) over a C-ABI HIP library (include/xclip.h, built by `python -m x_clip_amd.build`).
 """
 from .clip import CLIP, TextTransformer, VisionTransformer  # noqa: F401
+from .metrics import contrastive_metrics  # noqa: F401
 from .optim import FusedAdamW  # noqa: F401
 
 
@@ -33,4 +34,4 @@ def set_batch_invariant(on: bool = True) -> bool:
 _small_limit_saved = None
 
 
-__all__ = ["CLIP", "TextTransformer", "VisionTransformer", "FusedAdamW", "set_batch_invariant"]
+__all__ = ["CLIP", "TextTransformer", "VisionTransformer", "FusedAdamW", "contrastive_metrics", "set_batch_invariant"]

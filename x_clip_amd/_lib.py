@@ -89,12 +89,16 @@ _SIGNATURES = {
     "xclip_simloss_combine": (c_int, [P, L, L, P, P, P, F, P]),
     "xclip_simloss_fwd": (c_int, [P, P, L, L, L, F, P, L, I, F, P, P, P, P, I, P]),
     "xclip_simloss_grad": (c_int, [P, P, L, L, L, F, P, L, I, F, F, F, P, I, P, P, P, L, P, I, P]),
+    "xclip_simrank_workspace_bytes": (c_int64, [L, L]),
+    "xclip_simrank_pos": (c_int, [P, P, L, L, L, F, P, L, P, I, P]),
+    "xclip_simrank_partial": (c_int, [P, P, L, L, L, F, P, L, L, P, P, L, L, I, P]),
+    "xclip_simrank_combine": (c_int, [P, L, L, P, P, P, P]),
     "xclip_gradnorm_partial": (c_int, [P, L, L, I, P, P]),
     "xclip_optim_prepare": (c_int, [P, L, F, I, P, P, P, L, P]),
     "xclip_adamw_step": (c_int, [P, L, L, I, I, P, P, P, P, P, D, D, D, D, D, P]),
 }
 EXPORTS = tuple(_SIGNATURES)
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 
 def _bind(path: str):

@@ -440,6 +440,9 @@ class CLIP(nn.Module):
         # independent, so the result is the same; weight gradients are summed over the slices by autograd.
         self.image_micro_batches = 1
         self._streams = {}
+        # in-batch retrieval metrics of the training step (track_metrics): off by default -- no launch, no allocation
+        self._metric_ks = None
+        self.last_metrics = None
 
         self.sim_reg_loss_weight = sim_reg_loss_weight
         self.has_sim_reg_loss = sim_reg_loss_weight > 0.
@@ -449,6 +452,15 @@ class CLIP(nn.Module):
                              "x_clip.py:757-758,778)")
         if self.has_sim_reg_loss and use_all_token_embeds:
             raise NotImplementedError("sim_reg_loss_weight > 0 with use_all_token_embeds: only the CLS-latent form is on the accelerated path")
+
+    def track_metrics(self, ks=(1, 5, 10)):
+        """While enabled, every forward(..., return_loss=True) on the CLS head stores `self.last_metrics`: in-batch recall@k, mean rank
+        and hardest-negative margin of the step's first-view latents, text -> image and image -> text (x_clip_amd.metrics), computed
+        without the logits matrix and outside autograd -- loss and gradients are the same bits as without it.  track_metrics(None) turns
+        it off again.  The fine-grained head (use_all_token_embeds) has no latent per sample: last_metrics stays None there."""
+        self._metric_ks = None if ks is None else tuple(int(k) for k in ks)
+        self.last_metrics = None
+        return self
 
     def _side_stream(self, device, which=0):
         if device.type != "cuda":
@@ -652,6 +664,12 @@ class CLIP(nn.Module):
                                  text_latents_extra if self.extra_latent_projection else None,
                                  image_latents_extra if self.extra_latent_projection else None, text_mask, spec)
         else:
+            if self._metric_ks is not None:
+                from .metrics import contrastive_metrics
+                with torch.no_grad():
+                    self.last_metrics = contrastive_metrics(text_latents[0].detach(), image_latents[0].detach(), self.temperature.detach(),
+                                                            ks=self._metric_ks, distributed=self.requires_all_gather,
+                                                            assume_equal_batch=self.assume_equal_batch)
             loss = XL.contrastive_loss(self.temperature, text_latents, image_latents,
                                        text_latents_extra if self.extra_latent_projection else None,
                                        image_latents_extra if self.extra_latent_projection else None, spec)

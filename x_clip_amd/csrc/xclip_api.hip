@@ -21,6 +21,7 @@
 #include "kernels/rows.h"
 #include "kernels/simloss.h"
 #include "kernels/simloss5.h"
+#include "kernels/simrank.h"
 #include "kernels/sort.h"
 #include "kernels/tokens.h"
 
@@ -1422,6 +1423,68 @@ int xclip_simloss_fwd(const void* Q, const void* K, int64_t nq, int64_t nk, int6
     const int rc = xclip_simloss_partial(Q, K, nq, nk, d, scale, log_scale, diag_off, dcl, workspace, 0, slots, pos, dtype, stream);
     if (rc != 0) return rc;
     return xclip_simloss_combine(workspace, nq, slots, pos, lse, loss_accum, coef, stream);
+}
+
+// ---- in-batch retrieval metrics on the head's tile loop (kernels/simrank.h; reference x_clip.py:813-847) ----
+int64_t xclip_simrank_workspace_bytes(int64_t nq, int64_t nk) { return 3 * ((nk + 63) / 64) * nq * 4; }
+
+int xclip_simrank_pos(const void* Q, const void* K, int64_t nq, int64_t nk, int64_t d, float scale, const float* log_scale,
+                      int64_t diag_off, float* thr, int dtype, void* stream) {
+    XC_REQUIRE(dtype_ok(dtype), "bad dtype");
+    XC_REQUIRE(nq > 0 && nk > 0 && d > 0 && d % vec_of(dtype) == 0, "bad shape (d must be a multiple of the 16-byte chunk)");
+    XC_REQUIRE(nq < (1LL << 31) && nk < (1LL << 31) && diag_off > -(1LL << 31) && diag_off < (1LL << 31), "problem too large for 32-bit indices");
+    XC_REQUIRE(aligned16(Q) && aligned16(K) && thr != nullptr, "pointers must be 16-byte aligned / thr required");
+    dim3 grid((unsigned)((nq + 3) / 4)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == XCLIP_BF16)
+        hipLaunchKernelGGL((simrank_pos_kernel<bf16_t>), grid, block, 0, st, (const bf16_t*)Q, (const bf16_t*)K, (int)nq, (int)nk, (int)d, scale, log_scale, (int)diag_off, thr);
+    else
+        hipLaunchKernelGGL((simrank_pos_kernel<float>), grid, block, 0, st, (const float*)Q, (const float*)K, (int)nq, (int)nk, (int)d, scale, log_scale, (int)diag_off, thr);
+    return check_launch(__func__);
+}
+
+int xclip_simrank_partial(const void* Q, const void* K, int64_t nq, int64_t nk, int64_t d, float scale, const float* log_scale,
+                          int64_t diag_off, int64_t col0, const float* thr, void* workspace, int64_t tile_slot0, int64_t tile_slots,
+                          int dtype, void* stream) {
+    XC_REQUIRE(dtype_ok(dtype), "bad dtype");
+    XC_REQUIRE(nq > 0 && nk > 0 && d > 0 && d % vec_of(dtype) == 0, "bad shape (d must be a multiple of the 16-byte chunk)");
+    XC_REQUIRE(aligned16(Q) && aligned16(K) && workspace != nullptr && thr != nullptr, "pointers must be 16-byte aligned / workspace and thr required");
+    XC_REQUIRE(col0 >= 0 && col0 + nk < (1LL << 31) && nq < (1LL << 31) && diag_off > -(1LL << 31) && diag_off < (1LL << 31), "problem too large for 32-bit column indices");
+    XC_REQUIRE(tile_slot0 >= 0 && tile_slot0 + (nk + 63) / 64 <= tile_slots, "column slots out of range");
+    SimRankParams p;
+    memset(&p, 0, sizeof(p));
+    p.s.Q = Q; p.s.K = K; p.s.nq = (int)nq; p.s.nk = (int)nk; p.s.d = (int)d; p.s.scale = scale; p.s.log_scale = log_scale;
+    p.s.diag_off = (int)diag_off;
+    p.s.tiles_m = (int)((nq + 127) / 128); p.s.tiles_n = (int)((nk + 127) / 128);
+    p.thr = thr; p.col0 = (int)col0;
+    p.cnt = (uint32_t*)workspace + tile_slot0 * nq;
+    p.hmax = (float*)workspace + (tile_slots + tile_slot0) * nq;
+    p.harg = (int*)workspace + (2 * tile_slots + tile_slot0) * nq;
+    hipStream_t st = (hipStream_t)stream;
+    if (use_sim3(nq, nk, d, dtype)) {
+        XC_ALLOW_LDS(sim5_rank_kernel, G5_LDS_BYTES);
+        hipLaunchKernelGGL(sim5_rank_kernel, sim3_grid(nq, nk), dim3(G2_THREADS), G5_LDS_BYTES, st, p);
+        return check_launch(__func__);
+    }
+    dim3 grid(p.s.tiles_m * p.s.tiles_n), block(256);
+    if (dtype == XCLIP_BF16) {
+        XC_ALLOW_LDS((sim_rank_partial_kernel<bf16_t>), GemmCfg<bf16_t>::LDS_BYTES);
+        hipLaunchKernelGGL((sim_rank_partial_kernel<bf16_t>), grid, block, GemmCfg<bf16_t>::LDS_BYTES, st, p);
+    } else {
+        XC_ALLOW_LDS((sim_rank_partial_kernel<float>), GemmCfg<float>::LDS_BYTES);
+        hipLaunchKernelGGL((sim_rank_partial_kernel<float>), grid, block, GemmCfg<float>::LDS_BYTES, st, p);
+    }
+    return check_launch(__func__);
+}
+
+int xclip_simrank_combine(const void* workspace, int64_t nq, int64_t tile_slots, int32_t* rank, float* hard_val, int32_t* hard_idx,
+                          void* stream) {
+    XC_REQUIRE(nq > 0 && tile_slots > 0 && workspace != nullptr && rank != nullptr && hard_val != nullptr && hard_idx != nullptr, "bad arguments");
+    const uint32_t* cnt = (const uint32_t*)workspace;
+    hipLaunchKernelGGL(simrank_combine_kernel, dim3((unsigned)((nq + 63) / 64)), dim3(1024), 3 * 16 * 64 * 4, (hipStream_t)stream, cnt,
+                       (const float*)workspace + tile_slots * nq, (const int*)workspace + 2 * tile_slots * nq, rank, hard_val, hard_idx,
+                       (int)nq, (int)tile_slots);
+    return check_launch(__func__);
 }
 
 int xclip_simloss_grad(const void* Q, const void* K, int64_t nq, int64_t nk, int64_t d, float scale, const float* log_scale,

@@ -793,6 +793,79 @@ def simloss_chunked_fwd(q: Tensor, k_chunks, scale: float, diag_off: int, dcl: b
     return lse, pos
 
 
+def simrank(q: Tensor, k: Tensor, scale: float, diag_off: int, log_scale: Optional[Tensor] = None, thr: Optional[Tensor] = None):
+    """S = scale * exp(log_scale) * q k^T, never stored -> (rank [nq] int32: negatives j != i + diag_off with S_ij > thr[i], hard_val [nq]
+    fp32 / hard_idx [nq] int32: the hardest negative and its column (the lowest among equal maxima), thr [nq] fp32).  thr=None: the
+    row's positive S_{i, i + diag_off}, so that rank 0 = the positive beats every negative (the logits of x_clip.py:813-847)"""
+    return simrank_chunked(q, [(k, 0)], scale, diag_off, log_scale, thr)
+
+
+def simrank_chunked(q: Tensor, k_chunks, scale: float, diag_off: int, log_scale: Optional[Tensor] = None, thr: Optional[Tensor] = None,
+                    before_chunk=None):
+    """Same result as simrank(q, K) with K given as a list of (chunk [nk_c, d], first global column) in the order they should be
+    consumed; `before_chunk(c)` (optional) runs before chunk c is touched, e.g. to wait for its all-gather (simloss_chunked_fwd)."""
+    _dev_check(q, *[kc for kc, _ in k_chunks], log_scale, thr)
+    q = _c(q)
+    nq, d = q.shape
+    L = _lib.lib()
+    sc, lsp = _scale_args(scale, log_scale)
+    slots = sum((kc.shape[0] + 63) // 64 for kc, _ in k_chunks)
+    if nq == 0 or slots == 0:
+        # a rank without rows (or nothing to score against) launches nothing: every row has rank 0 and no hardest negative.  The
+        # hooks still run, so a pending all-gather is waited for as usual
+        for c in range(len(k_chunks) if before_chunk is not None else 0):
+            before_chunk(c)
+        return (torch.zeros(nq, dtype=torch.int32, device=q.device), torch.full((nq,), -3.0e38, dtype=torch.float32, device=q.device),
+                torch.full((nq,), -1, dtype=torch.int32, device=q.device),
+                torch.zeros(nq, dtype=torch.float32, device=q.device) if thr is None else thr)
+    ws = workspace(q.device, 3 * slots * nq * 4)
+    rank = torch.empty(nq, dtype=torch.int32, device=q.device)
+    hard_val = torch.empty(nq, dtype=torch.float32, device=q.device)
+    hard_idx = torch.empty(nq, dtype=torch.int32, device=q.device)
+    code, st = dtype_code(q), _stream(q)
+    own_thr = thr is None
+    if own_thr:
+        thr = torch.zeros(nq, dtype=torch.float32, device=q.device)
+    else:
+        assert thr.dtype == torch.float32 and thr.numel() == nq and thr.is_contiguous()
+
+    def positives_in(nk, col0):                                     # rows of q whose positive lies in columns [col0, col0 + nk)
+        return max(0, min(diag_off + nq, col0 + nk) - max(diag_off, col0))
+
+    # a chunk's sweep needs every row's threshold, whichever chunk holds that row's positive: sweeps wait until the chunks seen so far
+    # hold all the positives there are (the local chunk, first in line, holds them all when both sides are batched alike)
+    missing = sum(positives_in(kc.shape[0], col0) for kc, col0 in k_chunks) if own_thr else 0
+    pending, slot0 = [], 0
+    for c, (kc, col0) in enumerate(k_chunks):
+        if before_chunk is not None:
+            before_chunk(c)
+        kc = _c(kc)
+        nk = kc.shape[0]
+        assert kc.shape[1] == d and kc.dtype == q.dtype
+        if nk == 0:                                                 # a peer without rows: no columns, no slots
+            continue
+        if own_thr and positives_in(nk, col0) > 0:
+            _lib.check(L.xclip_simrank_pos(q.data_ptr(), kc.data_ptr(), nq, nk, d, sc, lsp, diag_off - col0, thr.data_ptr(), code, st),
+                       "xclip_simrank_pos")
+            missing -= positives_in(nk, col0)
+        pending.append((kc, col0, slot0))
+        slot0 += (nk + 63) // 64
+        if missing > 0:
+            continue
+        for kc, col0, s0 in pending:
+            nk = kc.shape[0]
+            probe = _probe(q)
+            ev0 = probe.begin(q) if probe is not None else None
+            _lib.check(L.xclip_simrank_partial(q.data_ptr(), kc.data_ptr(), nq, nk, d, sc, lsp, diag_off - col0, col0, thr.data_ptr(),
+                                               ws.data_ptr(), s0, slots, code, st), "xclip_simrank_partial")
+            if probe is not None:  # S = q k^T once; both latent sets and the thresholds in, three 4-byte partials per (row, slot) out
+                probe.end(q, ev0, "head", 2.0 * nq * nk * d, (nq + nk) * d * q.element_size() + 4 * nq + 12 * nq * ((nk + 63) // 64), "sim_rank")
+        pending = []
+    _lib.check(L.xclip_simrank_combine(ws.data_ptr(), nq, slots, rank.data_ptr(), hard_val.data_ptr(), hard_idx.data_ptr(), st),
+               "xclip_simrank_combine")
+    return rank, hard_val, hard_idx, thr
+
+
 def simloss_grad(q: Tensor, k: Tensor, scale: float, diag_off: int, dcl: bool, a: float, c: float, e: float, lse_q: Tensor,
                  lse_k: Tensor, dtau_accum: Optional[Tensor], log_scale: Optional[Tensor] = None, gmul: Optional[Tensor] = None,
                  times_scale: bool = False, out: Optional[Tensor] = None) -> Tensor:
