@@ -20,7 +20,7 @@ extern "C" {
 #endif
 
 enum { XCLIP_F32 = 0, XCLIP_BF16 = 1 };
-#define XCLIP_ABI_VERSION 25
+#define XCLIP_ABI_VERSION 26
 
 int xclip_abi_version(void);
 const char* xclip_last_error(void);
@@ -264,6 +264,31 @@ int xclip_simrank_partial(const void* Q, const void* K, int64_t nq, int64_t nk, 
 /* x_clip.py:813-847 */
 int xclip_simrank_combine(const void* workspace, int64_t nq, int64_t tile_slots, int32_t* rank, float* hard_val, int32_t* hard_idx,
                           void* stream);
+
+/* ---- pairwise sigmoid loss (Zhai et al., "Sigmoid Loss for Language Image Pre-Training", 2023; the reference has none) ---------
+ * Same Q, K, scale, log_scale and diag_off conventions as xclip_simloss_partial (diag_off is relative to the chunk); `bias` is a device
+ * fp32 scalar beta.  With t = scale * exp(*log_scale):
+ *   s_ij = t <Q_i, K_j>   (the similarity of x_clip.py:813-817)      l_ij = s_ij + beta      z_ij = +1 if j == i + diag_off else -1
+ *   rowloss_i = sum_j softplus(-z_ij l_ij)                           L = coef * sum_i rowloss_i            (coef = w / B_global)
+ *   G_ij = gmul * coef * (-z_ij) * sigma(-z_ij l_ij)                 dQ = t G K,  dK = t G^T Q,  dtau = sum G o s,  dbias = sum G
+ * `partial` writes one fp32 value per row and 64-column slot, sum_j softplus over the slot's valid columns, into slots [tile_slot0,
+ * tile_slot0 + ceil(nk/64)) of a workspace of tile_slots * nq floats (xclip_sigloss_workspace_bytes for one chunk) and nothing else.
+ * `combine` folds a row's slots in a fixed order into rowloss [nq] and adds coef * sum rowloss to *loss_accum (may be NULL) in a fixed
+ * order: the forward is deterministic.  `grad` writes G [nq, ldg] (storage dtype; t * G with g_times_scale; columns nk .. roundup(nk,
+ * chunk) are 0) and adds into *dtau_accum and *dbias_accum (float atomics; either may be NULL); gmul may be NULL (= 1).
+ * softplus(x) = max(x, 0) + log1p(exp(-|x|)) with log1p accurate relative to its argument, sigma from the same exponential: nothing
+ * overflows for any finite l.  The caller owns every buffer; nothing allocates, nothing synchronises. */
+int64_t xclip_sigloss_workspace_bytes(int64_t nq, int64_t nk);
+/* x_clip.py:813-817 */
+int xclip_sigloss_partial(const void* Q, const void* K, int64_t nq, int64_t nk, int64_t d, float scale, const float* log_scale,
+                          const float* bias, int64_t diag_off, void* workspace, int64_t tile_slot0, int64_t tile_slots, int dtype,
+                          void* stream);
+int xclip_sigloss_combine(const void* workspace, int64_t nq, int64_t tile_slots, float* rowloss, float* loss_accum, float coef,
+                          void* stream);
+/* x_clip.py:813-817 */
+int xclip_sigloss_grad(const void* Q, const void* K, int64_t nq, int64_t nk, int64_t d, float scale, const float* log_scale,
+                       const float* bias, int64_t diag_off, float coef, const float* gmul, int g_times_scale, void* G, int64_t ldg,
+                       float* dtau_accum, float* dbias_accum, int dtype, void* stream);
 
 /* ---- fine-grained (FILIP) head, use_all_token_embeds (x_clip.py:797-811) ----------------------------------------------------
  * The token similarity blocks come from xclip_gemm in chunks of `yc` images: S[(x, t), (y, k)] = <T[x,t], I[y0+y,k]> (no

@@ -93,12 +93,16 @@ _SIGNATURES = {
     "xclip_simrank_pos": (c_int, [P, P, L, L, L, F, P, L, P, I, P]),
     "xclip_simrank_partial": (c_int, [P, P, L, L, L, F, P, L, L, P, P, L, L, I, P]),
     "xclip_simrank_combine": (c_int, [P, L, L, P, P, P, P]),
+    "xclip_sigloss_workspace_bytes": (c_int64, [L, L]),
+    "xclip_sigloss_partial": (c_int, [P, P, L, L, L, F, P, P, L, P, L, L, I, P]),
+    "xclip_sigloss_combine": (c_int, [P, L, L, P, P, F, P]),
+    "xclip_sigloss_grad": (c_int, [P, P, L, L, L, F, P, P, L, F, P, I, P, L, P, P, I, P]),
     "xclip_gradnorm_partial": (c_int, [P, L, L, I, P, P]),
     "xclip_optim_prepare": (c_int, [P, L, F, I, P, P, P, L, P]),
     "xclip_adamw_step": (c_int, [P, L, L, I, I, P, P, P, P, P, D, D, D, D, D, P]),
 }
 EXPORTS = tuple(_SIGNATURES)
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 
 def _bind(path: str):

@@ -14,6 +14,7 @@ dimensions run in 64-feature head slots, 65 ... 128 in 128-feature slots, zero-p
 from __future__ import annotations
 
 import copy
+import math
 from typing import Optional
 
 import torch
@@ -314,9 +315,15 @@ class CLIP(nn.Module):
         multiview_loss_weight=0.1,
         checkpoint_during_training=False,
         sim_reg_loss_weight=0.,
+        sigmoid_loss=False,
+        sigmoid_init=(math.log(10.), -10.),
         **kwargs
     ):
         super().__init__()
+        # the pairwise sigmoid loss (Zhai et al. 2023) in place of InfoNCE: defined for one latent per sample and one pair of projections
+        assert not (sigmoid_loss and decoupled_contrastive_learning), 'sigmoid_loss is not defined together with decoupled_contrastive_learning (a softmax-denominator variant)'
+        assert not (sigmoid_loss and use_all_token_embeds), 'sigmoid_loss is not defined together with use_all_token_embeds (the fine-grained FILIP head)'
+        assert not (sigmoid_loss and (extra_latent_projection or sim_reg_loss_weight > 0.)), 'sigmoid_loss is not defined together with extra_latent_projection (and with it sim_reg_loss_weight): the loss has no direction'
         assert use_all_token_embeds or (visual_has_cls_token or text_has_cls_token), 'CLS token must be included on both vision and text transformers if you are not using fine-grained contrastive learning loss'
 
         self.dim_text = dim_text
@@ -409,6 +416,10 @@ class CLIP(nn.Module):
             self.to_visual_latent = nn.Linear(dim_image, dim_latent, bias=False)
 
         self.temperature = nn.Parameter(torch.tensor(1.))
+        self.sigmoid_loss = bool(sigmoid_loss)
+        if self.sigmoid_loss:                      # SigLIP's initialisation: t = 10, beta = -10
+            self.temperature = nn.Parameter(torch.tensor(float(sigmoid_init[0])))
+            self.logit_bias = nn.Parameter(torch.tensor(float(sigmoid_init[1]), dtype=self.temperature.dtype))
 
         self.use_all_token_embeds = use_all_token_embeds
         self.decoupled_contrastive_learning = decoupled_contrastive_learning
@@ -658,7 +669,7 @@ class CLIP(nn.Module):
 
         spec = XL.ContrastiveSpec(dcl=self.decoupled_contrastive_learning, main_weight=cl_loss_weight,
                                   multiview_weight=multiview_loss_weight, distributed=self.requires_all_gather,
-                                  assume_equal_batch=self.assume_equal_batch)
+                                  assume_equal_batch=self.assume_equal_batch, sigmoid=self.sigmoid_loss)
         if self.use_all_token_embeds:                                                      # x_clip.py:797-811
             loss = XL.filip_loss(self.temperature, text_latents, image_latents,
                                  text_latents_extra if self.extra_latent_projection else None,
@@ -670,9 +681,12 @@ class CLIP(nn.Module):
                     self.last_metrics = contrastive_metrics(text_latents[0].detach(), image_latents[0].detach(), self.temperature.detach(),
                                                             ks=self._metric_ks, distributed=self.requires_all_gather,
                                                             assume_equal_batch=self.assume_equal_batch)
-            loss = XL.contrastive_loss(self.temperature, text_latents, image_latents,
-                                       text_latents_extra if self.extra_latent_projection else None,
-                                       image_latents_extra if self.extra_latent_projection else None, spec)
+            if self.sigmoid_loss:
+                loss = XL.sigmoid_loss(self.temperature, self.logit_bias, text_latents, image_latents, spec)
+            else:
+                loss = XL.contrastive_loss(self.temperature, text_latents, image_latents,
+                                           text_latents_extra if self.extra_latent_projection else None,
+                                           image_latents_extra if self.extra_latent_projection else None, spec)
         if self.use_mlm:                                                                   # x_clip.py:857-860
             loss = loss + text_ssl_loss * self.text_ssl_loss_weight
         if self.use_visual_ssl:

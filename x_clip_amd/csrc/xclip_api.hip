@@ -22,6 +22,7 @@
 #include "kernels/simloss.h"
 #include "kernels/simloss5.h"
 #include "kernels/simrank.h"
+#include "kernels/sigloss.h"
 #include "kernels/sort.h"
 #include "kernels/tokens.h"
 
@@ -1484,6 +1485,102 @@ int xclip_simrank_combine(const void* workspace, int64_t nq, int64_t tile_slots,
     hipLaunchKernelGGL(simrank_combine_kernel, dim3((unsigned)((nq + 63) / 64)), dim3(1024), 3 * 16 * 64 * 4, (hipStream_t)stream, cnt,
                        (const float*)workspace + tile_slots * nq, (const int*)workspace + 2 * tile_slots * nq, rank, hard_val, hard_idx,
                        (int)nq, (int)tile_slots);
+    return check_launch(__func__);
+}
+
+// ---- pairwise sigmoid (SigLIP) loss on the head's tile loop (kernels/sigloss.h; similarity of x_clip.py:813-817) ----
+int64_t xclip_sigloss_workspace_bytes(int64_t nq, int64_t nk) { return ((nk + 63) / 64) * nq * 4; }
+
+static void sig_params(SigParams& p, const void* Q, const void* K, int64_t nq, int64_t nk, int64_t d, float scale, const float* log_scale,
+                       const float* bias, int64_t diag_off) {
+    memset(&p, 0, sizeof(p));
+    p.s.Q = Q; p.s.K = K; p.s.nq = (int)nq; p.s.nk = (int)nk; p.s.d = (int)d; p.s.scale = scale; p.s.log_scale = log_scale;
+    p.s.diag_off = (int)diag_off;
+    p.s.tiles_m = (int)((nq + 127) / 128); p.s.tiles_n = (int)((nk + 127) / 128);
+    p.bias = bias;
+}
+
+int xclip_sigloss_partial(const void* Q, const void* K, int64_t nq, int64_t nk, int64_t d, float scale, const float* log_scale,
+                          const float* bias, int64_t diag_off, void* workspace, int64_t tile_slot0, int64_t tile_slots, int dtype,
+                          void* stream) {
+    XC_REQUIRE(dtype_ok(dtype), "bad dtype");
+    XC_REQUIRE(nq > 0 && nk > 0 && d > 0 && d % vec_of(dtype) == 0, "bad shape (d must be a multiple of the 16-byte chunk)");
+    XC_REQUIRE(aligned16(Q) && aligned16(K) && workspace != nullptr && bias != nullptr, "pointers must be 16-byte aligned / workspace and bias required");
+    XC_REQUIRE(nq < (1LL << 31) && nk < (1LL << 31) && diag_off > -(1LL << 31) && diag_off < (1LL << 31), "problem too large for 32-bit indices");
+    XC_REQUIRE(tile_slot0 >= 0 && tile_slot0 + (nk + 63) / 64 <= tile_slots, "column slots out of range");
+    SigParams p;
+    sig_params(p, Q, K, nq, nk, d, scale, log_scale, bias, diag_off);
+    p.part = (float*)workspace + tile_slot0 * nq;
+    hipStream_t st = (hipStream_t)stream;
+    if (use_sim3(nq, nk, d, dtype)) {
+        XC_ALLOW_LDS(sig5_loss_kernel, G5_LDS_BYTES);
+        hipLaunchKernelGGL(sig5_loss_kernel, sim3_grid(nq, nk), dim3(G2_THREADS), G5_LDS_BYTES, st, p);
+        return check_launch(__func__);
+    }
+    dim3 grid(p.s.tiles_m * p.s.tiles_n), block(256);
+    if (dtype == XCLIP_BF16) {
+        XC_ALLOW_LDS((sig_partial_kernel<bf16_t>), GemmCfg<bf16_t>::LDS_BYTES);
+        hipLaunchKernelGGL((sig_partial_kernel<bf16_t>), grid, block, GemmCfg<bf16_t>::LDS_BYTES, st, p);
+    } else {
+        XC_ALLOW_LDS((sig_partial_kernel<float>), GemmCfg<float>::LDS_BYTES);
+        hipLaunchKernelGGL((sig_partial_kernel<float>), grid, block, GemmCfg<float>::LDS_BYTES, st, p);
+    }
+    return check_launch(__func__);
+}
+
+int xclip_sigloss_combine(const void* workspace, int64_t nq, int64_t tile_slots, float* rowloss, float* loss_accum, float coef,
+                          void* stream) {
+    XC_REQUIRE(nq > 0 && nq < (1LL << 31) && tile_slots > 0 && workspace != nullptr && rowloss != nullptr, "bad arguments");
+    hipLaunchKernelGGL(sigloss_combine_kernel, dim3((unsigned)((nq + 63) / 64)), dim3(1024), 16 * 64 * 4, (hipStream_t)stream,
+                       (const float*)workspace, rowloss, (int)nq, (int)tile_slots);
+    if (loss_accum != nullptr)
+        hipLaunchKernelGGL(sigloss_total_kernel, dim3(1), dim3(1024), 16 * 4, (hipStream_t)stream, (const float*)rowloss, loss_accum, (int)nq, coef);
+    return check_launch(__func__);
+}
+
+int xclip_sigloss_grad(const void* Q, const void* K, int64_t nq, int64_t nk, int64_t d, float scale, const float* log_scale,
+                       const float* bias, int64_t diag_off, float coef, const float* gmul, int g_times_scale, void* G, int64_t ldg,
+                       float* dtau_accum, float* dbias_accum, int dtype, void* stream) {
+    XC_REQUIRE(dtype_ok(dtype), "bad dtype");
+    const int vec = vec_of(dtype);
+    XC_REQUIRE(nq > 0 && nk > 0 && d > 0 && d % vec == 0, "bad shape (d must be a multiple of the 16-byte chunk)");
+    XC_REQUIRE(ldg % vec == 0 && ldg >= (nk + vec - 1) / vec * vec, "ldg must cover nk rounded up to the chunk");
+    XC_REQUIRE(aligned16(Q) && aligned16(K) && aligned16(G) && bias != nullptr, "pointers must be 16-byte aligned / bias required");
+    XC_REQUIRE(nq < (1LL << 31) && nk < (1LL << 31) && diag_off > -(1LL << 31) && diag_off < (1LL << 31), "problem too large for 32-bit indices");
+    SigParams p;
+    sig_params(p, Q, K, nq, nk, d, scale, log_scale, bias, diag_off);
+    p.s.gmul = gmul; p.s.g_times_scale = g_times_scale; p.s.G = G; p.s.ldg = ldg; p.s.dtau = dtau_accum;
+    p.coef = coef; p.dbias = dbias_accum;
+    hipStream_t st = (hipStream_t)stream;
+    if (use_sim3(nq, nk, d, dtype)) {
+        // every full 256 x 256 tile on the ring loop; tiles at a ragged edge, if there are any, through the general epilogue over a tile
+        // list in a second launch (xclip_simloss_grad)
+        XC_REQUIRE(255 * ldg * 2 + 512 < (1LL << 32), "ldg too large for the line stores");
+        if (nq >= G2_BM && nk >= G2_BN) {
+            if (nq * ldg * 2 > (48LL << 20)) {                      // G larger than the L2s can hold anyway: streamed stores
+                XC_ALLOW_LDS(sig5_grad_kernel<true>, G5_LDS_BYTES);
+                hipLaunchKernelGGL(sig5_grad_kernel<true>, sim3_grid(nq, nk), dim3(G2_THREADS), G5_LDS_BYTES, st, p);
+            } else {
+                XC_ALLOW_LDS(sig5_grad_kernel<false>, G5_LDS_BYTES);
+                hipLaunchKernelGGL(sig5_grad_kernel<false>, sim3_grid(nq, nk), dim3(G2_THREADS), G5_LDS_BYTES, st, p);
+            }
+        }
+        const int64_t tm = (nq + G2_BM - 1) / G2_BM, tn = (nk + G2_BN - 1) / G2_BN;
+        const int64_t nedge = ((nk % G2_BN) ? tm : 0) + ((nq % G2_BM) ? tn : 0);    // Sim5EdgeTiles::count
+        if (nedge == 0) return check_launch(__func__);
+        const int cus = xc_num_cus();
+        XC_ALLOW_LDS(sig5_grad_edge_kernel, G2_LDS_BYTES);
+        hipLaunchKernelGGL(sig5_grad_edge_kernel, dim3((unsigned)(nedge < cus ? nedge : cus)), dim3(G2_THREADS), G2_LDS_BYTES, st, p);
+        return check_launch(__func__);
+    }
+    dim3 grid(p.s.tiles_m * p.s.tiles_n), block(256);
+    if (dtype == XCLIP_BF16) {
+        XC_ALLOW_LDS((sig_grad_kernel<bf16_t>), GemmCfg<bf16_t>::LDS_BYTES);
+        hipLaunchKernelGGL((sig_grad_kernel<bf16_t>), grid, block, GemmCfg<bf16_t>::LDS_BYTES, st, p);
+    } else {
+        XC_ALLOW_LDS((sig_grad_kernel<float>), GemmCfg<float>::LDS_BYTES);
+        hipLaunchKernelGGL((sig_grad_kernel<float>), grid, block, GemmCfg<float>::LDS_BYTES, st, p);
+    }
     return check_launch(__func__);
 }
 

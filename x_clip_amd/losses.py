@@ -34,6 +34,7 @@ class ContrastiveSpec:
     distributed: bool = False             # requires_all_gather (x_clip.py:591)
     group: object = None                  # process group (None = default)
     assume_equal_batch: bool = False      # skip the per-step size exchange (distributed.py:17-21)
+    sigmoid: bool = False                 # pairwise sigmoid loss instead of InfoNCE / DCL (sigmoid_loss; the reference has none)
 
 
 _TWICE = ("x_clip_amd: this loss was already back-propagated and the state of its head (latent views, log-sum-exps, arg-max maps) was "
@@ -45,6 +46,40 @@ def _acc_gemm(acc: Optional[Tensor], a: Tensor, b: Tensor, M: int, N: int, K: in
     if acc is None:
         return ops.gemm(a, b, M, N, K, a_kmajor=a_kmajor, b_kmajor=True)
     return ops.gemm(a, b, M, N, K, a_kmajor=a_kmajor, b_kmajor=True, residual=acc, out=acc)
+
+
+def _exchange(spec: ContrastiveSpec, mats, b: int, dev):
+    """cross-rank exchange of the latent views (x_clip.py:759-769) -> sizes, rank, first global row of this rank, global batch,
+    {name: GatheredViews} (empty in a single process)"""
+    if not spec.distributed:
+        return [b], 0, 0, b, {}
+    sizes = [b] * xdist.dist.get_world_size(spec.group) if spec.assume_equal_batch else xdist.exchange_sizes(b, dev, spec.group)
+    rank = xdist.dist.get_rank(spec.group)
+    return sizes, rank, sum(sizes[:rank]), sum(sizes), {name: xdist.GatheredViews(views, sizes, spec.group) for name, views in mats.items()}
+
+
+def _column_chunks(spec: ContrastiveSpec, mats, gathered, name: str, view: int, sizes, rank: int, v: int):
+    """the column chunks of one view for a G block -> [(K, first global column)], [owning rank | None].  Ragged per-rank batches
+    (distributed.py:23-37; a chunk would start off a 16-byte boundary inside G): the peers' blocks compacted into one chunk, rank None"""
+    if not spec.distributed:
+        return [(mats[name][view], 0)], [rank]
+    chunks = gathered[name].chunks(view)
+    order = [rank] + [r for r in range(len(sizes)) if r != rank]
+    if all(s % v == 0 for s in sizes):
+        return chunks, order
+    by_rank = {r: ch for ch, r in zip(chunks, order)}
+    return [(torch.cat([by_rank[r][0] for r in range(len(sizes))], dim=0), 0)], [None]
+
+
+def _stack_views(grads, b: int, d: int, dt, dev) -> Tensor:
+    """per-view gradient blocks (None = no contribution) -> [views, b, d]"""
+    out = torch.empty(len(grads), b, d, dtype=dt, device=dev)
+    for k, g in enumerate(grads):
+        if g is None:
+            out[k].zero_()
+        else:
+            ops.copy_rows(g, out[k])
+    return out
 
 
 class _ContrastiveFn(torch.autograd.Function):
@@ -59,17 +94,7 @@ class _ContrastiveFn(torch.autograd.Function):
         if extra:
             mats["Tx"] = [ops._c(Tx[v]) for v in range(m)]
             mats["Ix"] = [ops._c(Ix[v]) for v in range(n)]
-        # ---- cross-rank exchange (x_clip.py:759-769) ----
-        gathered = {}
-        if spec.distributed:
-            sizes = [b] * xdist.dist.get_world_size(spec.group) if spec.assume_equal_batch else \
-                xdist.exchange_sizes(b, dev, spec.group)
-            rank = xdist.dist.get_rank(spec.group)
-            off, B = sum(sizes[:rank]), sum(sizes)
-            for name, views in mats.items():
-                gathered[name] = xdist.GatheredViews(views, sizes, spec.group)
-        else:
-            sizes, rank, off, B = [b], 0, 0, b
+        sizes, rank, off, B, gathered = _exchange(spec, mats, b, dev)
 
         def kchunks(name, v):
             return gathered[name].chunks(v) if spec.distributed else [(mats[name][v], 0)]
@@ -135,8 +160,6 @@ class _ContrastiveFn(torch.autograd.Function):
         gmul = dloss.detach().reshape(1).float().contiguous()
         dtau = torch.zeros(1, dtype=torch.float32, device=dev)
         grads = {name: [None] * len(views) for name, views in mats.items()}
-        offsets = [sum(sizes[:r]) for r in range(len(sizes))]
-        aligned = all(s % v == 0 for s in sizes)    # else: chunk columns would start off a 16-byte boundary inside G
 
         def lse_chunk(idx, r):
             return lse_all[r, idx, : sizes[r]] if spec.distributed else lse_local[idx]
@@ -146,13 +169,7 @@ class _ContrastiveFn(torch.autograd.Function):
             Q = mats[qn][qv]
             ldg = (B + v - 1) // v * v
             G = torch.empty(b, ldg, dtype=dt, device=dev)
-            chunks = gathered[kn].chunks(kv) if spec.distributed else [(mats[kn][kv], 0)]
-            order = [rank] + [r for r in range(len(sizes)) if r != rank]
-            if spec.distributed and not aligned:
-                # ragged per-rank batches (distributed.py:23-37): compact the peers' blocks once and treat them as one chunk
-                by_rank = {r: ch for ch, r in zip(chunks, order)}
-                chunks = [(torch.cat([by_rank[r][0] for r in range(len(sizes))], dim=0), 0)]
-                order = [None]
+            chunks, order = _column_chunks(spec, mats, gathered, kn, kv, sizes, rank, v)
             zero_q = None
             for (K, col0), r in zip(chunks, order):
                 if lse_q_idx >= 0:
@@ -186,15 +203,7 @@ class _ContrastiveFn(torch.autograd.Function):
             xdist.all_reduce_scalars(dtau, spec.group)
 
         def stack(name, count):
-            if name not in grads:
-                return None
-            out = torch.empty(count, b, d, dtype=dt, device=dev)
-            for k, g in enumerate(grads[name]):
-                if g is None:
-                    out[k].zero_()
-                else:
-                    ops.copy_rows(g, out[k])
-            return out
+            return _stack_views(grads[name], b, d, dt, dev) if name in grads else None
 
         ctx.mats = ctx.gathered = ctx.lse_local = ctx.lse_all = None
         need = ctx.needs_input_grad
@@ -209,7 +218,103 @@ def contrastive_loss(tau: Tensor, text_latents: Tensor, image_latents: Tensor, t
     loss = main_weight * L[0, 0] + multiview_weight * mean(other view pairs)   (x_clip.py:812-868, CLS mode)."""
     assert text_latents.dim() == 3 and image_latents.dim() == 3 and text_latents.shape[1:] == image_latents.shape[1:]
     assert (text_latents_extra is None) == (image_latents_extra is None)
+    assert not spec.sigmoid, "spec.sigmoid selects the pairwise sigmoid loss: call sigmoid_loss (it takes the logit bias)"
     return _ContrastiveFn.apply(spec, tau, text_latents, image_latents, text_latents_extra, image_latents_extra)
+
+
+# =========================================================================================================================
+# pairwise sigmoid loss (Zhai et al., "Sigmoid Loss for Language Image Pre-Training", 2023; the reference has none)
+# =========================================================================================================================
+class _SigmoidFn(torch.autograd.Function):
+    """L = sum over view pairs w_p / B sum_ij softplus(-z_ij (e^tau <T_i, I_j> + beta)), z = +1 on the diagonal of the GLOBAL batch, else
+    -1.  Every logit is an independent binary term and the loss has no direction: rows of T go against all of I, once.  Two passes as
+    _ContrastiveFn: the forward stores nothing but rowloss partials (csrc/kernels/sigloss.h), the backward writes G once and feeds
+    two GEMMs.  With a process group the latents are all-gathered and peers' chunks consumed as they arrive; no vector crosses ranks."""
+
+    @staticmethod
+    def forward(ctx, spec: ContrastiveSpec, tau: Tensor, bias: Tensor, T: Tensor, I: Tensor):
+        m, b, d = T.shape
+        n = I.shape[0]
+        dev = T.device
+        tau32 = tau.detach().reshape(1).float().contiguous()
+        bias32 = bias.detach().reshape(1).float().contiguous()
+        mats = {"T": [ops._c(T[v]) for v in range(m)], "I": [ops._c(I[v]) for v in range(n)]}
+        sizes, rank, off, B, gathered = _exchange(spec, mats, b, dev)
+        npairs = m * n
+        loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        plan = []                                 # (i, j, coef)
+        for i in range(m):
+            for j in range(n):
+                w = spec.main_weight if (i == 0 and j == 0) else spec.multiview_weight / max(npairs - 1, 1)
+                coef = w / B
+                if coef != 0.0:
+                    ops.sigloss_chunked_fwd(mats["T"][i], gathered["I"].chunks(j) if spec.distributed else [(mats["I"][j], 0)], 1.0, off,
+                                            coef, loss, log_scale=tau32, bias=bias32,
+                                            before_chunk=(lambda c: gathered["I"].wait() if c == 1 else None) if spec.distributed else None)
+                    plan.append((i, j, coef))
+        if spec.distributed:
+            for g in gathered.values():
+                g.wait()
+            xdist.all_reduce_scalars(loss, spec.group)
+        ctx.spec, ctx.plan, ctx.mats, ctx.gathered = spec, plan, mats, gathered
+        ctx.tau32, ctx.bias32, ctx.geom = tau32, bias32, (m, n, b, d, B, off, sizes, rank, tau.dtype, bias.dtype)
+        return loss.reshape(())
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dloss):
+        if ctx.mats is None:
+            raise RuntimeError(_TWICE)
+        spec, plan, mats, gathered, tau32, bias32 = ctx.spec, ctx.plan, ctx.mats, ctx.gathered, ctx.tau32, ctx.bias32
+        m, n, b, d, B, off, sizes, rank, tau_dtype, bias_dtype = ctx.geom
+        dev = tau32.device
+        dt = mats["T"][0].dtype
+        v = ops.vec(dt)
+        gmul = dloss.detach().reshape(1).float().contiguous()
+        dtau = torch.zeros(1, dtype=torch.float32, device=dev)
+        dbias = torch.zeros(1, dtype=torch.float32, device=dev)
+        grads = {name: [None] * len(views) for name, views in mats.items()}
+
+        def block(qn, qv, kn, kv, coef, want_acc):
+            """G for the local rows of mats[qn][qv] against every column chunk of kn/kv, then dQ += G K."""
+            Q = mats[qn][qv]
+            ldg = (B + v - 1) // v * v
+            G = torch.empty(b, ldg, dtype=dt, device=dev)
+            chunks, _ = _column_chunks(spec, mats, gathered, kn, kv, sizes, rank, v)
+            for K, col0 in chunks:
+                if K.shape[0] == 0:                 # a peer without rows
+                    continue
+                ops.sigloss_grad(Q, K, 1.0, off - col0, coef, dtau if want_acc else None, dbias if want_acc else None,
+                                 log_scale=tau32, bias=bias32, gmul=gmul, times_scale=True,
+                                 out=G[:, col0: col0 + (K.shape[0] + v - 1) // v * v])
+                grads[qn][qv] = _acc_gemm(grads[qn][qv], G[:, col0: col0 + K.shape[0]], K, b, d, K.shape[0], a_kmajor=False)
+            return G
+
+        for (i, j, coef) in (plan if b > 0 else []):    # a rank without rows launches nothing
+            # block A: local T rows vs all I  ->  dT (and, single process, dI through G^T)
+            G = block("T", i, "I", j, coef, True)
+            if spec.distributed:
+                # block B: local I rows vs all T -> dI; dtau and dbias already counted by the row blocks
+                block("I", j, "T", i, coef, False)
+            else:
+                grads["I"][j] = _acc_gemm(grads["I"][j], G[:, :b], mats["T"][i], b, d, b, a_kmajor=True)
+            del G
+        if spec.distributed:
+            xdist.all_reduce_scalars(dtau, spec.group)
+            xdist.all_reduce_scalars(dbias, spec.group)
+
+        ctx.mats = ctx.gathered = None
+        need = ctx.needs_input_grad
+        return (None, dtau.reshape(()).to(tau_dtype) if need[1] else None, dbias.reshape(()).to(bias_dtype) if need[2] else None,
+                _stack_views(grads["T"], b, d, dt, dev) if need[3] else None, _stack_views(grads["I"], b, d, dt, dev) if need[4] else None)
+
+
+def sigmoid_loss(tau: Tensor, bias: Tensor, text_latents: Tensor, image_latents: Tensor, spec: ContrastiveSpec) -> Tensor:
+    """text_latents [m, b, d], image_latents [n, b, d] (l2-normalised), tau = log-temperature, bias = logit bias (scalars) -> fp32 scalar
+    loss = main_weight * L[0, 0] + multiview_weight * mean(other view pairs), L[i, j] = 1 / B sum softplus(-z (e^tau T_i I_j^T + bias))."""
+    assert text_latents.dim() == 3 and image_latents.dim() == 3 and text_latents.shape[1:] == image_latents.shape[1:]
+    assert spec.sigmoid and not spec.dcl, "the pairwise sigmoid loss is not defined together with decoupled_contrastive_learning"
+    return _SigmoidFn.apply(spec, tau, bias, text_latents, image_latents)
 
 
 # =========================================================================================================================

@@ -897,6 +897,94 @@ def simloss_grad(q: Tensor, k: Tensor, scale: float, diag_off: int, dcl: bool, a
     return G
 
 
+# ---- pairwise sigmoid (SigLIP) head --------------------------------------------------------------------------------------------
+def _bias_arg(bias: Tensor) -> int:
+    assert bias is not None and bias.dtype == torch.float32 and bias.numel() == 1
+    return bias.data_ptr()
+
+
+def sigloss_fwd(q: Tensor, k: Tensor, scale: float, diag_off: int, coef: float, loss_accum: Optional[Tensor],
+                log_scale: Optional[Tensor] = None, bias: Optional[Tensor] = None) -> Tensor:
+    """l = scale * exp(log_scale) * q k^T + bias -> rowloss [nq] fp32 = sum_j softplus(-z_ij l_ij), z = +1 at j = i + diag_off, else -1;
+    loss_accum (fp32 scalar) += coef * sum(rowloss).  `bias`: fp32 scalar on the device."""
+    return sigloss_chunked_fwd(q, [(k, 0)], scale, diag_off, coef, loss_accum, log_scale, bias)
+
+
+def sigloss_chunked_fwd(q: Tensor, k_chunks, scale: float, diag_off: int, coef: float, loss_accum: Optional[Tensor],
+                        log_scale: Optional[Tensor] = None, bias: Optional[Tensor] = None, before_chunk=None,
+                        out: Optional[Tensor] = None) -> Tensor:
+    """Same result as sigloss_fwd(q, K) with K given as a list of (chunk [nk_c, d], first global column) in the order they should be
+    consumed; `before_chunk(c)` (optional) runs before chunk c is launched, e.g. to wait for its all-gather (simloss_chunked_fwd).
+    `out`: a contiguous fp32 [nq] tensor to receive rowloss."""
+    _dev_check(q, *[kc for kc, _ in k_chunks], loss_accum, log_scale, bias, out)
+    q = _c(q)
+    nq, d = q.shape
+    L = _lib.lib()
+    sc, lsp = _scale_args(scale, log_scale)
+    bp = _bias_arg(bias)
+    if out is not None:
+        assert out.dtype == torch.float32 and out.shape == (nq,) and out.is_contiguous()
+    slots = sum((kc.shape[0] + 63) // 64 for kc, _ in k_chunks)
+    if nq == 0 or slots == 0:
+        # a rank without rows (or nothing to score against) launches nothing; the hooks still run, so a pending all-gather is waited for
+        for c in range(len(k_chunks) if before_chunk is not None else 0):
+            before_chunk(c)
+        return torch.zeros(nq, dtype=torch.float32, device=q.device) if out is None else out.zero_()
+    ws = workspace(q.device, slots * nq * 4)
+    rowloss = torch.empty(nq, dtype=torch.float32, device=q.device) if out is None else out
+    slot0 = 0
+    for c, (kc, col0) in enumerate(k_chunks):
+        if before_chunk is not None:
+            before_chunk(c)
+        kc = _c(kc)
+        nk = kc.shape[0]
+        assert kc.shape[1] == d and kc.dtype == q.dtype
+        if nk == 0:                                                 # a peer without rows: no columns, no slots
+            continue
+        probe = _probe(q)
+        ev0 = probe.begin(q) if probe is not None else None
+        _lib.check(L.xclip_sigloss_partial(q.data_ptr(), kc.data_ptr(), nq, nk, d, sc, lsp, bp, diag_off - col0, ws.data_ptr(), slot0, slots,
+                                           dtype_code(q), _stream(q)), "xclip_sigloss_partial")
+        if probe is not None:      # S = q k^T once; both latent sets in, one fp32 partial per (row, 64-column slot) out
+            probe.end(q, ev0, "head", 2.0 * nq * nk * d, (nq + nk) * d * q.element_size() + 4 * nq * ((nk + 63) // 64), "sig_fwd")
+        slot0 += (nk + 63) // 64
+    _lib.check(L.xclip_sigloss_combine(ws.data_ptr(), nq, slots, rowloss.data_ptr(), _ptr(loss_accum), coef, _stream(q)),
+               "xclip_sigloss_combine")
+    return rowloss
+
+
+def sigloss_grad(q: Tensor, k: Tensor, scale: float, diag_off: int, coef: float, dtau_accum: Optional[Tensor],
+                 dbias_accum: Optional[Tensor], log_scale: Optional[Tensor] = None, bias: Optional[Tensor] = None,
+                 gmul: Optional[Tensor] = None, times_scale: bool = False, out: Optional[Tensor] = None) -> Tensor:
+    """-> G [nq, nk rounded up to the chunk] in q.dtype, G_ij = gmul * coef * (-z_ij) * sigmoid(-z_ij l_ij) (padding columns are zero);
+    dtau_accum += sum(G * S), dbias_accum += sum(G).  `out`: a [nq, >= roundup(nk)] view (unit inner stride) to write into."""
+    _dev_check(q, k, dtau_accum, dbias_accum, log_scale, bias, gmul, out)
+    q, k = _c(q), _c(k)
+    nq, d = q.shape
+    nk = k.shape[0]
+    v = vec(q.dtype)
+    ldg = (nk + v - 1) // v * v
+    if out is None:
+        G = torch.empty(nq, ldg, dtype=q.dtype, device=q.device)
+    else:
+        G = out
+        assert G.dim() == 2 and G.stride(1) == 1 and G.shape[0] == nq and G.shape[1] >= ldg and G.dtype == q.dtype
+    if gmul is not None:
+        assert gmul.dtype == torch.float32 and gmul.numel() == 1
+    sc, lsp = _scale_args(scale, log_scale)
+    bp = _bias_arg(bias)
+    if nq == 0 or nk == 0:                                          # a rank / a peer without rows: nothing to launch
+        return G
+    probe = _probe(q)
+    ev0 = probe.begin(q) if probe is not None else None
+    _lib.check(_lib.lib().xclip_sigloss_grad(q.data_ptr(), k.data_ptr(), nq, nk, d, sc, lsp, bp, diag_off, float(coef), _ptr(gmul),
+                                             int(times_scale), G.data_ptr(), G.stride(0), _ptr(dtau_accum), _ptr(dbias_accum),
+                                             dtype_code(q), _stream(q)), "xclip_sigloss_grad")
+    if probe is not None:          # S recomputed once; both latent sets in, G out
+        probe.end(q, ev0, "head", 2.0 * nq * nk * d, (nq + nk) * d * q.element_size() + nq * ldg * q.element_size(), "sig_grad")
+    return G
+
+
 # ---- fine-grained (FILIP) head -----------------------------------------------------------------------------------------------
 def filip_reduce(S: Tensor, mask: Tensor, log_temp: Tensor, t2i: Tensor, i2t: Tensor, kmax: Tensor, tmax: Tensor, cnt: Tensor,
                  nt: int, ni: int, yc: int, y0: int):
