@@ -253,6 +253,52 @@ def test_simloss_chunked(dtype, dcl):
     K.case_simloss_chunked(DEV, dtype, dcl)
 
 
+def test_chunked_head_hook_contract():
+    """The chunk loop under the three chunked head ops: `before_chunk(c)` once per chunk, in order, an empty chunk included; the result
+    equals the single-chunk call on the concatenated columns; the sigmoid and rank ops, which take empty inputs, still run the hooks
+    for a call without rows and return their neutral results.  (InfoNCE refuses empty inputs in the C layer: chunks of 3 / 4.)
+    Counts, maxima, columns and the positive are the same bits.  The fp32 sums are grouped by 64-column slot, and the chunks put the 7
+    columns into two slots where the single call has one: 7 terms regrouped differ by at most 7 x 2^-24 = 4.2e-7 of a row's sum (the
+    log-sum-exp: the same of exp(lse - max), i.e. that much absolute), the 5 rows' total likewise -- bound 1e-6."""
+    def same(a, b):
+        torch.testing.assert_close(a, b, rtol=1e-6, atol=1e-6)
+
+    ops = K.ops
+    g = torch.Generator().manual_seed(11)
+    q = torch.nn.functional.normalize(torch.randn(5, 8, generator=g), dim=-1)
+    k = torch.nn.functional.normalize(torch.randn(7, 8, generator=g), dim=-1)
+    tau, bias = torch.tensor([1.5]), torch.tensor([-2.0])
+    three, two = [(k[:3], 0), (k[3:3], 3), (k[3:], 3)], [(k[:3], 0), (k[3:], 3)]
+
+    calls, loss, loss1 = [], torch.zeros(1), torch.zeros(1)
+    got = ops.simloss_chunked_fwd(q, two, 1.0, 1, False, 0.5, loss, log_scale=tau, before_chunk=calls.append)
+    want = ops.simloss_chunked_fwd(q, [(k, 0)], 1.0, 1, False, 0.5, loss1, log_scale=tau)
+    assert calls == [0, 1]
+    same(got[0], want[0]), same(loss, loss1)
+    assert torch.equal(got[1], want[1])
+
+    calls, loss, loss1 = [], torch.zeros(1), torch.zeros(1)
+    got = ops.sigloss_chunked_fwd(q, three, 1.0, 1, 0.5, loss, log_scale=tau, bias=bias, before_chunk=calls.append)
+    want = ops.sigloss_chunked_fwd(q, [(k, 0)], 1.0, 1, 0.5, loss1, log_scale=tau, bias=bias)
+    assert calls == [0, 1, 2]
+    same(got, want), same(loss, loss1)
+
+    calls = []
+    got = ops.simrank_chunked(q, three, 1.0, 1, log_scale=tau, before_chunk=calls.append)
+    want = ops.simrank_chunked(q, [(k, 0)], 1.0, 1, log_scale=tau)
+    assert calls == [0, 1, 2]
+    assert all(torch.equal(a, b) for a, b in zip(got, want))
+
+    calls, loss = [], torch.zeros(1)
+    got = ops.sigloss_chunked_fwd(q[:0], three, 1.0, 1, 0.5, loss, log_scale=tau, bias=bias, before_chunk=calls.append)
+    assert calls == [0, 1, 2] and got.shape == (0,) and got.dtype == torch.float32 and loss.item() == 0.0
+    calls = []
+    rank, hard_val, hard_idx, thr = ops.simrank_chunked(q[:0], three, 1.0, 1, log_scale=tau, before_chunk=calls.append)
+    assert calls == [0, 1, 2]
+    assert rank.shape == hard_val.shape == hard_idx.shape == thr.shape == (0,)
+    assert rank.dtype == torch.int32 and hard_val.dtype == torch.float32 and hard_idx.dtype == torch.int32 and thr.dtype == torch.float32
+
+
 @pytest.fixture
 def big_gemm_kernels():
     """shapes that gemm_small.h would take stay on the 256 x 256 kernels these tests are about"""

@@ -111,13 +111,7 @@ struct SigLossEpilogue {
         }
     }
     XC_DEV int with_scratch(f32x16 (&acc)[4][2], int m0, int n0, unsigned char*) const {
-        const SimParams& s = p.s;
-        const int lane = threadIdx.x & 63;
-        const int wave = uniform(threadIdx.x >> 6), wm = wave >> 2, wn = wave & 3;
-        const int c0 = n0 + wn * 64;                               // this wave's 64-column slot
-        if (c0 >= s.nk) return 0;
-        if (sim5_full_tile(s, m0, n0) && sim5_off_diagonal(s, m0, n0)) tile<true>(acc, m0, c0, wm, lane);
-        else tile<false>(acc, m0, c0, wm, lane);
+        sim5_slot_tile(*this, p.s, acc, m0, n0);
         return 0;
     }
 };
@@ -137,11 +131,8 @@ __global__ __launch_bounds__(256) void sig_partial_kernel(SigParams p) {
     const SimParams& s = p.s;
     const float* Cs = reinterpret_cast<const float*>(lds);
     const int tid = threadIdx.x;
-    const int tile = xcd_remap(blockIdx.x, s.tiles_m * s.tiles_n);
-    const int tn = tile % s.tiles_n;
-    const int m0 = (tile / s.tiles_n) * GEMM_BM, n0 = tn * GEMM_BN;
-    gemm_mainloop<T, false, false>(reinterpret_cast<const T*>(s.Q), s.d, reinterpret_cast<const T*>(s.K), s.d, s.nq, s.nk,
-                                   m0, n0, 0, s.d, lds);
+    int m0, n0, tn;
+    sim_general_tile<T>(s, lds, m0, n0, tn);
     const float scale2 = sim_scale(s) * SIG_LOG2E, bias2 = *p.bias * SIG_LOG2E;
     const int row = tid >> 1, half = tid & 1;
     const int gm = m0 + row;
@@ -244,24 +235,7 @@ struct SigGradEpilogue {
     XC_DEV int with_scratch(f32x16 (&acc)[4][2], int m0, int n0, unsigned char* scratch) {
         if (!sim5_full_tile(p.s, m0, n0)) return 0;                 // (uniform) the edge launch's tile
         to_g(acc, m0, n0);
-        // (the line exchange and its 16 stores: Sim5FastGradEpilogue::with_scratch, which says why the lane id is opaque)
-        const int lane = (int)opaque((uint32_t)(threadIdx.x & 63));
-        const int wave = uniform(threadIdx.x >> 6), wm = wave >> 2, wn = wave & 3;
-        const G4GemmEpilogue<G4_PLAIN> lines{gp};
-        const BufRsrc rc = make_rsrc(gp.C + (long)m0 * gp.ldc + n0, 255u * (uint32_t)gp.ldc * 2u + 512u);
-        const uint32_t vc = ((uint32_t)(wm * 128 + (lane >> 3)) * (uint32_t)gp.ldc + (uint32_t)(wn * 64 + 8 * (lane & 7))) * 2u;
-        const uint32_t s8 = (uint32_t)gp.ldc * 16u;                  // 8 rows * ldc * 2 bytes
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            u32x4 o[4];
-            lines.template pack_lines_i<true>(acc[i], scratch, o, lane);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (STREAM) buf_st16_nt<0>(rc, vc, s8 * (uint32_t)(4 * i + k), o[k]);
-                else buf_st16<0>(rc, vc, s8 * (uint32_t)(4 * i + k), o[k]);
-            }
-        }
-        return 16;                                                   // younger than the next tile's first operand pieces (g5_run: in_flight == 16)
+        return sim5_store_g_lines<STREAM>(acc, gp, m0, n0, scratch);
     }
     // Per logit: one fma (l2), a bare v_exp_f32, an add and a v_rcp_f32, a compare-and-select for the numerator, two multiplies, and
     // an fma and an add for the two sums.  A tile that holds a piece of the positive diagonal (uniform test; O(tiles_m) tiles) saves the
@@ -394,10 +368,7 @@ struct SigGradEdgeEpilogue {
 template <bool STREAM>
 __global__ __launch_bounds__(G2_THREADS, 2) void sig5_grad_kernel(SigParams p) {
     XC_LDS_DYNAMIC(lds);
-    Gemm2Params g = sim3_gemm_params(p.s);
-    g.C = reinterpret_cast<bf16_t*>(p.s.G);
-    g.ldc = p.s.ldg;
-    g.stream_out = STREAM;
+    const Gemm2Params g = sim5_g_gemm_params(p.s, STREAM);
     const float scale = sim_scale(p.s);
     const float gc = (p.s.gmul != nullptr ? *p.s.gmul : 1.0f) * p.coef * (p.s.g_times_scale ? scale : 1.0f);
     g5_run<false, false, SigGradEpilogue<STREAM>>(g, lds, SigGradEpilogue<STREAM>{p, g, scale, *p.bias * SIG_LOG2E, gc, reinterpret_cast<float*>(lds)});
@@ -416,10 +387,8 @@ __global__ __launch_bounds__(256) void sig_grad_kernel(SigParams p) {
     const SimParams& s = p.s;
     const float* Cs = reinterpret_cast<const float*>(lds);
     const int tid = threadIdx.x;
-    const int tile = xcd_remap(blockIdx.x, s.tiles_m * s.tiles_n);
-    const int m0 = (tile / s.tiles_n) * GEMM_BM, n0 = (tile % s.tiles_n) * GEMM_BN;
-    gemm_mainloop<T, false, false>(reinterpret_cast<const T*>(s.Q), s.d, reinterpret_cast<const T*>(s.K), s.d, s.nq, s.nk,
-                                   m0, n0, 0, s.d, lds);
+    int m0, n0, tn;
+    sim_general_tile<T>(s, lds, m0, n0, tn);
     constexpr int CPR = 128 / VEC;
     T* G = reinterpret_cast<T*>(s.G);
     const float scale = sim_scale(s);

@@ -45,17 +45,26 @@ constexpr float SIM_NEG = -3.0e38f;
 
 XC_DEV float sim_scale(const SimParams& p) { return p.log_scale != nullptr ? p.scale * expf(*p.log_scale) : p.scale; }
 
+// the general form's prologue (every general kernel of the head, here and in simrank.h / sigloss.h): the work-group's tile -> its origin
+// and column tile, then the raw Q K^T tile as fp32 in LDS
+template <typename T>
+XC_DEV void sim_general_tile(const SimParams& p, unsigned char* lds, int& m0, int& n0, int& tn) {
+    const int tile = xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
+    tn = tile % p.tiles_n;
+    m0 = (tile / p.tiles_n) * GEMM_BM;
+    n0 = tn * GEMM_BN;
+    gemm_mainloop<T, false, false>(reinterpret_cast<const T*>(p.Q), p.d, reinterpret_cast<const T*>(p.K), p.d, p.nq, p.nk,
+                                   m0, n0, 0, p.d, lds);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void sim_lse_partial_kernel(SimParams p) {
     constexpr int LDC = GemmCfg<T>::LDC;
     XC_LDS_DYNAMIC(lds);
     const float* Cs = reinterpret_cast<const float*>(lds);
     const int tid = threadIdx.x;
-    const int tile = xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
-    const int tn = tile % p.tiles_n;
-    const int m0 = (tile / p.tiles_n) * GEMM_BM, n0 = tn * GEMM_BN;
-    gemm_mainloop<T, false, false>(reinterpret_cast<const T*>(p.Q), p.d, reinterpret_cast<const T*>(p.K), p.d, p.nq, p.nk,
-                                   m0, n0, 0, p.d, lds);
+    int m0, n0, tn;
+    sim_general_tile<T>(p, lds, m0, n0, tn);
     // two threads per row, 64 columns each, then one shuffle to merge the pair
     const float scale = sim_scale(p);
     const int row = tid >> 1, half = tid & 1;
@@ -139,10 +148,8 @@ __global__ __launch_bounds__(256) void sim_grad_kernel(SimParams p) {
     XC_LDS_DYNAMIC(lds);
     const float* Cs = reinterpret_cast<const float*>(lds);
     const int tid = threadIdx.x;
-    const int tile = xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
-    const int m0 = (tile / p.tiles_n) * GEMM_BM, n0 = (tile % p.tiles_n) * GEMM_BN;
-    gemm_mainloop<T, false, false>(reinterpret_cast<const T*>(p.Q), p.d, reinterpret_cast<const T*>(p.K), p.d, p.nq, p.nk,
-                                   m0, n0, 0, p.d, lds);
+    int m0, n0, tn;
+    sim_general_tile<T>(p, lds, m0, n0, tn);
     constexpr int CPR = 128 / VEC;
     T* G = reinterpret_cast<T*>(p.G);
     const float scale = sim_scale(p);

@@ -43,8 +43,62 @@ struct Sim5LseEpilogue {
 XC_DEV bool sim5_full_tile(const SimParams& p, int m0, int n0) { return (m0 + G2_BM <= p.nq) && (n0 + G2_BN <= p.nk); }
 XC_DEV bool sim5_off_diagonal(const SimParams& p, int m0, int n0) { return m0 + p.diag_off + G2_BM <= n0 || m0 + p.diag_off >= n0 + G2_BN; }
 
+// the Gemm2Params of a G launch: C = G, ldc = ldg, alpha = 1 -- what the line stores address
+XC_DEV Gemm2Params sim5_g_gemm_params(const SimParams& p, bool stream) {
+    Gemm2Params g = sim3_gemm_params(p);
+    g.C = reinterpret_cast<bf16_t*>(p.G);
+    g.ldc = p.ldg;
+    g.stream_out = stream;
+    return g;
+}
+
+// A full tile whose accumulators have become G leaves through the plain GEMM's line exchange as 16 whole-line stores (both grad
+// epilogues, here and in sigloss.h).  -> the stores left in flight: they are YOUNGER than the A / B pieces the next tile's first K step
+// waits for and may stay in flight over it (g5_run: in_flight == 16).
 // (STREAM -- non-temporal stores for a G the L2s cannot hold anyway -- is a template parameter: as a run-time branch around the 16
-//  stores it cost this kernel 102 spilled registers)
+//  stores it cost the InfoNCE kernel 102 spilled registers)
+// (an opaque lane id: what is derived from it below is recomputed per tile, not carried across the K loop in spilled registers --
+//  round 6: twelve scratch reloads per tile, each behind s_waitcnt vmcnt(0), i.e. a drain of the next tile's DMA pieces and of the
+//  previous group's stores; profiles/r06_k_*.  PLAIN_LANE: the round-5 form, for the A/B of the measurement build)
+template <bool STREAM, bool PLAIN_LANE = false>
+XC_DEV int sim5_store_g_lines(f32x16 (&acc)[4][2], const Gemm2Params& gp, int m0, int n0, unsigned char* scratch) {
+    const int lane = PLAIN_LANE ? (int)(threadIdx.x & 63) : (int)opaque((uint32_t)(threadIdx.x & 63));
+    const int wave = uniform(threadIdx.x >> 6), wm = wave >> 2, wn = wave & 3;
+    const G4GemmEpilogue<G4_PLAIN> lines{gp};
+    const BufRsrc rc = make_rsrc(gp.C + (long)m0 * gp.ldc + n0, 255u * (uint32_t)gp.ldc * 2u + 512u);
+    const uint32_t vc = ((uint32_t)(wm * 128 + (lane >> 3)) * (uint32_t)gp.ldc + (uint32_t)(wn * 64 + 8 * (lane & 7))) * 2u;
+    const uint32_t s8 = (uint32_t)gp.ldc * 16u;                  // 8 rows * ldc * 2 bytes
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        u32x4 o[4];
+        lines.template pack_lines_i<true>(acc[i], scratch, o, lane);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (STREAM) buf_st16_nt<0>(rc, vc, s8 * (uint32_t)(4 * i + k), o[k]);
+            else buf_st16<0>(rc, vc, s8 * (uint32_t)(4 * i + k), o[k]);
+        }
+    }
+    return 16;
+}
+
+// The slot epilogues (SigLossEpilogue, Sim5RankEpilogue: one partial per row and 64-column slot): the wave's slot, and whether the tile
+// takes the epilogue's plain form -- an interior tile off the diagonal, no range or diagonal tests -- or the general one.
+// -> true when the plain form ran (a wave whose slot lies beyond the last column does nothing)
+template <typename Epilogue>
+XC_DEV bool sim5_slot_tile(const Epilogue& ep, const SimParams& s, f32x16 (&acc)[4][2], int m0, int n0) {
+    const int lane = threadIdx.x & 63;
+    const int wave = uniform(threadIdx.x >> 6), wm = wave >> 2, wn = wave & 3;
+    const int c0 = n0 + wn * 64;                                   // this wave's 64-column slot
+    if (c0 >= s.nk) return false;
+    if (sim5_full_tile(s, m0, n0) && sim5_off_diagonal(s, m0, n0)) {
+        ep.template tile<true>(acc, m0, c0, wm, lane);
+        return true;
+    }
+    ep.template tile<false>(acc, m0, c0, wm, lane);
+    return false;
+}
+
+// (STREAM: sim5_store_g_lines)
 // (VAR: measurement build only, XCLIP_SIMG -- 1 = without DEFER_FRAGS, 2 = without the spread vote / exact form (round-3 arithmetic), 3 = both,
 //  4 = the exchange addresses hoisted and spilled as before round 6)
 template <bool STREAM, int VAR = 0>
@@ -67,28 +121,7 @@ struct Sim5FastGradEpilogue {
     XC_DEV int with_scratch(f32x16 (&acc)[4][2], int m0, int n0, unsigned char* scratch) {
         if (!sim5_full_tile(p, m0, n0)) return 0;                   // (uniform) the edge launch's tile
         to_g(acc, m0, n0);
-        // (an opaque lane id: what is derived from it below is recomputed per tile, not carried across the K loop in spilled registers --
-        //  round 6: twelve scratch reloads per tile, each behind s_waitcnt vmcnt(0), i.e. a drain of the next tile's DMA pieces and of the
-        //  previous group's stores; profiles/r06_k_*)
-        const int lane = (VAR & 4) ? (int)(threadIdx.x & 63) : (int)opaque((uint32_t)(threadIdx.x & 63));      // (VAR 4: the round-5 form, for the A/B)
-        const int wave = uniform(threadIdx.x >> 6), wm = wave >> 2, wn = wave & 3;
-        const G4GemmEpilogue<G4_PLAIN> lines{gp};
-        const BufRsrc rc = make_rsrc(gp.C + (long)m0 * gp.ldc + n0, 255u * (uint32_t)gp.ldc * 2u + 512u);
-        const uint32_t vc = ((uint32_t)(wm * 128 + (lane >> 3)) * (uint32_t)gp.ldc + (uint32_t)(wn * 64 + 8 * (lane & 7))) * 2u;
-        const uint32_t s8 = (uint32_t)gp.ldc * 16u;                  // 8 rows * ldc * 2 bytes
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            u32x4 o[4];
-            lines.template pack_lines_i<true>(acc[i], scratch, o, lane);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (STREAM) buf_st16_nt<0>(rc, vc, s8 * (uint32_t)(4 * i + k), o[k]);
-                else buf_st16<0>(rc, vc, s8 * (uint32_t)(4 * i + k), o[k]);
-            }
-        }
-        // the 16 stores are YOUNGER than the A / B pieces the next tile's first K step waits for and may stay in flight over it
-        // (g5_run: in_flight == 16)
-        return 16;
+        return sim5_store_g_lines<STREAM, (VAR & 4) != 0>(acc, gp, m0, n0, scratch);      // (VAR 4: the round-5 lane form, for the A/B)
     }
     // The accumulators of a full tile become G in place.  Per logit: G = exp(s - R) (a' + c') with s = acc * scale,
     // a' = gs a exp(R - lse_q), c' = gs c exp(R - lse_k) -- ONE exponential per logit, in the base-2 domain: one fma + a bare v_exp_f32;
@@ -253,10 +286,7 @@ struct Sim5EdgeTiles {
 template <bool STREAM, int VAR = 0>
 __global__ __launch_bounds__(G2_THREADS, 2) void sim5_grad_fast_kernel(SimParams p) {
     XC_LDS_DYNAMIC(lds);
-    Gemm2Params g = sim3_gemm_params(p);
-    g.C = reinterpret_cast<bf16_t*>(p.G);
-    g.ldc = p.ldg;
-    g.stream_out = STREAM;
+    const Gemm2Params g = sim5_g_gemm_params(p, STREAM);
     g5_run<false, false, Sim5FastGradEpilogue<STREAM, VAR>>(g, lds, Sim5FastGradEpilogue<STREAM, VAR>{p, g, sim_scale(p), p.gmul != nullptr ? *p.gmul : 1.0f});
 }
 __global__ __launch_bounds__(G2_THREADS, 2) void sim5_grad_edge_kernel(SimParams p) {
@@ -333,10 +363,7 @@ __global__ __launch_bounds__(G2_THREADS, 2) void sim5_lse_kernel(SimParams p) {
 #ifdef XCLIP_MEASURE
 __global__ __launch_bounds__(G2_THREADS, 2) void sim5_grad_kernel(SimParams p) {
     XC_LDS_DYNAMIC(lds);
-    Gemm2Params g = sim3_gemm_params(p);
-    g.C = reinterpret_cast<bf16_t*>(p.G);
-    g.ldc = p.ldg;
-    g.stream_out = (long)p.nq * p.ldg * 2 > (48L << 20);             // G larger than the L2s can hold anyway: streamed stores
+    const Gemm2Params g = sim5_g_gemm_params(p, (long)p.nq * p.ldg * 2 > (48L << 20));     // G larger than the L2s can hold anyway: streamed stores
     g5_run<false, false, Sim5GradEpilogue>(g, lds, Sim5GradEpilogue{p, g, Sim3GradEpilogue{p}});
 }
 #endif

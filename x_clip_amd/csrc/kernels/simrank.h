@@ -98,17 +98,7 @@ struct Sim5RankEpilogue {
         }
     }
     XC_DEV int with_scratch(f32x16 (&acc)[4][2], int m0, int n0, unsigned char*) const {
-        const SimParams& s = p.s;
-        const int lane = threadIdx.x & 63;
-        const int wave = uniform(threadIdx.x >> 6), wm = wave >> 2, wn = wave & 3;
-        const int c0 = n0 + wn * 64;                               // this wave's 64-column slot
-        if (c0 >= s.nk) return 0;
-        if (sim5_full_tile(s, m0, n0) && sim5_off_diagonal(s, m0, n0)) {
-            tile<true>(acc, m0, c0, wm, lane);
-            return 8;                                              // vector-memory instructions left behind
-        }
-        tile<false>(acc, m0, c0, wm, lane);
-        return 0;
+        return sim5_slot_tile(*this, p.s, acc, m0, n0) ? 8 : 0;   // a plain tile's vector-memory instructions left behind
     }
 };
 
@@ -127,11 +117,8 @@ __global__ __launch_bounds__(256) void sim_rank_partial_kernel(SimRankParams p) 
     const SimParams& s = p.s;
     const float* Cs = reinterpret_cast<const float*>(lds);
     const int tid = threadIdx.x;
-    const int tile = xcd_remap(blockIdx.x, s.tiles_m * s.tiles_n);
-    const int tn = tile % s.tiles_n;
-    const int m0 = (tile / s.tiles_n) * GEMM_BM, n0 = tn * GEMM_BN;
-    gemm_mainloop<T, false, false>(reinterpret_cast<const T*>(s.Q), s.d, reinterpret_cast<const T*>(s.K), s.d, s.nq, s.nk,
-                                   m0, n0, 0, s.d, lds);
+    int m0, n0, tn;
+    sim_general_tile<T>(s, lds, m0, n0, tn);
     const float scale = sim_scale(s);
     const int row = tid >> 1, half = tid & 1;
     const int gm = m0 + row;

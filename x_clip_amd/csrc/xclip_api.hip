@@ -1373,37 +1373,97 @@ extern "C++" inline dim3 sim3_grid(int64_t nq, int64_t nk) {
     return dim3((unsigned)(tiles < cus ? tiles : cus));
 }
 
-int xclip_simloss_partial(const void* Q, const void* K, int64_t nq, int64_t nk, int64_t d, float scale, const float* log_scale,
-                          int64_t diag_off, int dcl, void* workspace, int64_t tile_slot0, int64_t tile_slots, float* pos, int dtype, void* stream) {
-    XC_REQUIRE(dtype_ok(dtype), "bad dtype");
-    XC_REQUIRE(nq > 0 && nk > 0 && d > 0 && d % vec_of(dtype) == 0, "bad shape (d must be a multiple of the 16-byte chunk)");
-    XC_REQUIRE(aligned16(Q) && aligned16(K) && workspace != nullptr, "pointers must be 16-byte aligned / workspace required");
+// ---- what the six head entry points share (InfoNCE, rank and sigmoid; partial / pos / grad) ----
+extern "C++" {
+// -> what is wrong with the arguments, or null.  nq, nk and diag_off become int fields of SimParams.
+static const char* sim_bad_args(const void* Q, const void* K, int64_t nq, int64_t nk, int64_t d, int64_t diag_off, int dtype) {
+    if (!dtype_ok(dtype)) return "bad dtype";
+    if (!(nq > 0 && nk > 0 && d > 0 && d % vec_of(dtype) == 0)) return "bad shape (d must be a multiple of the 16-byte chunk)";
+    if (!(aligned16(Q) && aligned16(K))) return "Q and K must be 16-byte aligned";
+    if (!(nq < (1LL << 31) && nk < (1LL << 31) && d < (1LL << 31) && diag_off > -(1LL << 31) && diag_off < (1LL << 31)))
+        return "problem too large for 32-bit indices";
+    return nullptr;
+}
+// the same for G of the two grads
+static const char* sim_bad_g(const void* G, int64_t ldg, int64_t nq, int64_t nk, int64_t d, int dtype) {
+    const int vec = vec_of(dtype);
+    if (!(ldg % vec == 0 && ldg >= (nk + vec - 1) / vec * vec)) return "ldg must cover nk rounded up to the chunk";
+    if (!aligned16(G)) return "G must be 16-byte aligned";
+    if (use_sim3(nq, nk, d, dtype) && !(255 * ldg * 2 + 512 < (1LL << 32))) return "ldg too large for the line stores";
+    return nullptr;
+}
+#define XC_SIM_REQUIRE(what) do { if (const char* bad_ = (what)) return xcapi::fail(__func__, bad_); } while (0)
+
+// the forward's fields; everything else zero
+static SimParams sim_params(const void* Q, const void* K, int64_t nq, int64_t nk, int64_t d, float scale, const float* log_scale,
+                            int64_t diag_off, int dcl) {
     SimParams p;
     memset(&p, 0, sizeof(p));
     p.Q = Q; p.K = K; p.nq = (int)nq; p.nk = (int)nk; p.d = (int)d; p.scale = scale; p.log_scale = log_scale;
     p.diag_off = (int)diag_off; p.dcl = dcl;
     p.tiles_m = (int)((nq + 127) / 128); p.tiles_n = (int)((nk + 127) / 128);
+    return p;
+}
+
+// one launch over every tile: the general kernel of the dtype.  (The kernels are template arguments: XC_ALLOW_LDS keeps one flag per kernel.)
+template <typename P, void (*GENERAL_BF16)(P), void (*GENERAL_F32)(P)>
+static void sim_launch_general(const P& p, const SimParams& s, int dtype, hipStream_t st) {
+    dim3 grid(s.tiles_m * s.tiles_n), block(256);
+    if (dtype == XCLIP_BF16) {
+        XC_ALLOW_LDS(*GENERAL_BF16, GemmCfg<bf16_t>::LDS_BYTES);
+        hipLaunchKernelGGL(GENERAL_BF16, grid, block, GemmCfg<bf16_t>::LDS_BYTES, st, p);
+    } else {
+        XC_ALLOW_LDS(*GENERAL_F32, GemmCfg<float>::LDS_BYTES);
+        hipLaunchKernelGGL(GENERAL_F32, grid, block, GemmCfg<float>::LDS_BYTES, st, p);
+    }
+}
+// ... or the ring kernel where use_sim3 takes the problem (the three partials)
+template <typename P, void (*RING)(P), void (*GENERAL_BF16)(P), void (*GENERAL_F32)(P)>
+static void sim_launch(const P& p, const SimParams& s, int dtype, hipStream_t st) {
+    if (!use_sim3(s.nq, s.nk, s.d, dtype)) return sim_launch_general<P, GENERAL_BF16, GENERAL_F32>(p, s, dtype, st);
+    XC_ALLOW_LDS(*RING, G5_LDS_BYTES);
+    hipLaunchKernelGGL(RING, sim3_grid(s.nq, s.nk), dim3(G2_THREADS), G5_LDS_BYTES, st, p);
+}
+
+// G of a use_sim3 problem (simloss5.h): every full 256 x 256 tile (on the diagonal or off it) on the ring loop with a spill-free epilogue
+// of its own -- streamed stores for a G larger than the L2s can hold anyway -- if there is a full tile at all; tiles at a ragged edge, if
+// there are any, through the general epilogue over a tile list (Sim5EdgeTiles) in a second launch.
+// (without_full / without_edge: the measurement build's split of the two)
+template <typename P, void (*FULL_STREAMED)(P), void (*FULL)(P), void (*EDGE)(P)>
+static void sim_launch_g(const P& p, const SimParams& s, hipStream_t st, bool without_full = false, bool without_edge = false) {
+    const int64_t nq = s.nq, nk = s.nk;
+    if (!without_full && nq >= G2_BM && nk >= G2_BN) {
+        if (nq * s.ldg * 2 > (48LL << 20)) {
+            XC_ALLOW_LDS(*FULL_STREAMED, G5_LDS_BYTES);
+            hipLaunchKernelGGL(FULL_STREAMED, sim3_grid(nq, nk), dim3(G2_THREADS), G5_LDS_BYTES, st, p);
+        } else {
+            XC_ALLOW_LDS(*FULL, G5_LDS_BYTES);
+            hipLaunchKernelGGL(FULL, sim3_grid(nq, nk), dim3(G2_THREADS), G5_LDS_BYTES, st, p);
+        }
+    }
+    const int64_t tm = (nq + G2_BM - 1) / G2_BM, tn = (nk + G2_BN - 1) / G2_BN;
+    const int64_t nedge = ((nk % G2_BN) ? tm : 0) + ((nq % G2_BM) ? tn : 0);    // Sim5EdgeTiles::count
+    if (without_edge || nedge == 0) return;
+    const int cus = xc_num_cus();
+    XC_ALLOW_LDS(*EDGE, G2_LDS_BYTES);
+    hipLaunchKernelGGL(EDGE, dim3((unsigned)(nedge < cus ? nedge : cus)), dim3(G2_THREADS), G2_LDS_BYTES, st, p);
+}
+}  // extern "C++"
+
+int xclip_simloss_partial(const void* Q, const void* K, int64_t nq, int64_t nk, int64_t d, float scale, const float* log_scale,
+                          int64_t diag_off, int dcl, void* workspace, int64_t tile_slot0, int64_t tile_slots, float* pos, int dtype, void* stream) {
+    XC_SIM_REQUIRE(sim_bad_args(Q, K, nq, nk, d, diag_off, dtype));
+    XC_REQUIRE(workspace != nullptr, "workspace required");
     XC_REQUIRE(tile_slot0 >= 0 && tile_slot0 + (nk + 63) / 64 <= tile_slots, "column slots out of range");
+    SimParams p = sim_params(Q, K, nq, nk, d, scale, log_scale, diag_off, dcl);
     p.part_m = (float*)workspace + tile_slot0 * nq; p.part_l = (float*)workspace + (tile_slots + tile_slot0) * nq; p.pos = pos;
     hipStream_t st = (hipStream_t)stream;
-    if (use_sim3(nq, nk, d, dtype)) {
-        static const int gen = measure_env("XCLIP_SIM", 5);      // measurement build: 3 = the round-1 two-stage loop (simloss3.h)
-        if (gen == 3) {
-            XC_ALLOW_LDS(sim3_lse_kernel, G2_LDS_BYTES);
-            hipLaunchKernelGGL(sim3_lse_kernel, sim3_grid(nq, nk), dim3(G2_THREADS), G2_LDS_BYTES, st, p);
-        } else {
-            XC_ALLOW_LDS(sim5_lse_kernel, G5_LDS_BYTES);
-            hipLaunchKernelGGL(sim5_lse_kernel, sim3_grid(nq, nk), dim3(G2_THREADS), G5_LDS_BYTES, st, p);
-        }
-        return check_launch(__func__);
-    }
-    dim3 grid(p.tiles_m * p.tiles_n), block(256);
-    if (dtype == XCLIP_BF16) {
-        XC_ALLOW_LDS((sim_lse_partial_kernel<bf16_t>), GemmCfg<bf16_t>::LDS_BYTES);
-        hipLaunchKernelGGL((sim_lse_partial_kernel<bf16_t>), grid, block, GemmCfg<bf16_t>::LDS_BYTES, st, p);
+    static const int gen = measure_env("XCLIP_SIM", 5);          // measurement build: 3 = the round-1 two-stage loop (simloss3.h)
+    if (gen == 3 && use_sim3(nq, nk, d, dtype)) {
+        XC_ALLOW_LDS(sim3_lse_kernel, G2_LDS_BYTES);
+        hipLaunchKernelGGL(sim3_lse_kernel, sim3_grid(nq, nk), dim3(G2_THREADS), G2_LDS_BYTES, st, p);
     } else {
-        XC_ALLOW_LDS((sim_lse_partial_kernel<float>), GemmCfg<float>::LDS_BYTES);
-        hipLaunchKernelGGL((sim_lse_partial_kernel<float>), grid, block, GemmCfg<float>::LDS_BYTES, st, p);
+        sim_launch<SimParams, sim5_lse_kernel, sim_lse_partial_kernel<bf16_t>, sim_lse_partial_kernel<float>>(p, p, dtype, st);
     }
     return check_launch(__func__);
 }
@@ -1431,10 +1491,8 @@ int64_t xclip_simrank_workspace_bytes(int64_t nq, int64_t nk) { return 3 * ((nk 
 
 int xclip_simrank_pos(const void* Q, const void* K, int64_t nq, int64_t nk, int64_t d, float scale, const float* log_scale,
                       int64_t diag_off, float* thr, int dtype, void* stream) {
-    XC_REQUIRE(dtype_ok(dtype), "bad dtype");
-    XC_REQUIRE(nq > 0 && nk > 0 && d > 0 && d % vec_of(dtype) == 0, "bad shape (d must be a multiple of the 16-byte chunk)");
-    XC_REQUIRE(nq < (1LL << 31) && nk < (1LL << 31) && diag_off > -(1LL << 31) && diag_off < (1LL << 31), "problem too large for 32-bit indices");
-    XC_REQUIRE(aligned16(Q) && aligned16(K) && thr != nullptr, "pointers must be 16-byte aligned / thr required");
+    XC_SIM_REQUIRE(sim_bad_args(Q, K, nq, nk, d, diag_off, dtype));
+    XC_REQUIRE(thr != nullptr, "thr required");
     dim3 grid((unsigned)((nq + 3) / 4)), block(256);
     hipStream_t st = (hipStream_t)stream;
     if (dtype == XCLIP_BF16)
@@ -1447,34 +1505,18 @@ int xclip_simrank_pos(const void* Q, const void* K, int64_t nq, int64_t nk, int6
 int xclip_simrank_partial(const void* Q, const void* K, int64_t nq, int64_t nk, int64_t d, float scale, const float* log_scale,
                           int64_t diag_off, int64_t col0, const float* thr, void* workspace, int64_t tile_slot0, int64_t tile_slots,
                           int dtype, void* stream) {
-    XC_REQUIRE(dtype_ok(dtype), "bad dtype");
-    XC_REQUIRE(nq > 0 && nk > 0 && d > 0 && d % vec_of(dtype) == 0, "bad shape (d must be a multiple of the 16-byte chunk)");
-    XC_REQUIRE(aligned16(Q) && aligned16(K) && workspace != nullptr && thr != nullptr, "pointers must be 16-byte aligned / workspace and thr required");
-    XC_REQUIRE(col0 >= 0 && col0 + nk < (1LL << 31) && nq < (1LL << 31) && diag_off > -(1LL << 31) && diag_off < (1LL << 31), "problem too large for 32-bit column indices");
+    XC_SIM_REQUIRE(sim_bad_args(Q, K, nq, nk, d, diag_off, dtype));
+    XC_REQUIRE(workspace != nullptr && thr != nullptr, "workspace and thr required");
+    XC_REQUIRE(col0 >= 0 && col0 + nk < (1LL << 31), "problem too large for 32-bit column indices");
     XC_REQUIRE(tile_slot0 >= 0 && tile_slot0 + (nk + 63) / 64 <= tile_slots, "column slots out of range");
     SimRankParams p;
     memset(&p, 0, sizeof(p));
-    p.s.Q = Q; p.s.K = K; p.s.nq = (int)nq; p.s.nk = (int)nk; p.s.d = (int)d; p.s.scale = scale; p.s.log_scale = log_scale;
-    p.s.diag_off = (int)diag_off;
-    p.s.tiles_m = (int)((nq + 127) / 128); p.s.tiles_n = (int)((nk + 127) / 128);
+    p.s = sim_params(Q, K, nq, nk, d, scale, log_scale, diag_off, 0);
     p.thr = thr; p.col0 = (int)col0;
     p.cnt = (uint32_t*)workspace + tile_slot0 * nq;
     p.hmax = (float*)workspace + (tile_slots + tile_slot0) * nq;
     p.harg = (int*)workspace + (2 * tile_slots + tile_slot0) * nq;
-    hipStream_t st = (hipStream_t)stream;
-    if (use_sim3(nq, nk, d, dtype)) {
-        XC_ALLOW_LDS(sim5_rank_kernel, G5_LDS_BYTES);
-        hipLaunchKernelGGL(sim5_rank_kernel, sim3_grid(nq, nk), dim3(G2_THREADS), G5_LDS_BYTES, st, p);
-        return check_launch(__func__);
-    }
-    dim3 grid(p.s.tiles_m * p.s.tiles_n), block(256);
-    if (dtype == XCLIP_BF16) {
-        XC_ALLOW_LDS((sim_rank_partial_kernel<bf16_t>), GemmCfg<bf16_t>::LDS_BYTES);
-        hipLaunchKernelGGL((sim_rank_partial_kernel<bf16_t>), grid, block, GemmCfg<bf16_t>::LDS_BYTES, st, p);
-    } else {
-        XC_ALLOW_LDS((sim_rank_partial_kernel<float>), GemmCfg<float>::LDS_BYTES);
-        hipLaunchKernelGGL((sim_rank_partial_kernel<float>), grid, block, GemmCfg<float>::LDS_BYTES, st, p);
-    }
+    sim_launch<SimRankParams, sim5_rank_kernel, sim_rank_partial_kernel<bf16_t>, sim_rank_partial_kernel<float>>(p, p.s, dtype, (hipStream_t)stream);
     return check_launch(__func__);
 }
 
@@ -1491,40 +1533,18 @@ int xclip_simrank_combine(const void* workspace, int64_t nq, int64_t tile_slots,
 // ---- pairwise sigmoid (SigLIP) loss on the head's tile loop (kernels/sigloss.h; similarity of x_clip.py:813-817) ----
 int64_t xclip_sigloss_workspace_bytes(int64_t nq, int64_t nk) { return ((nk + 63) / 64) * nq * 4; }
 
-static void sig_params(SigParams& p, const void* Q, const void* K, int64_t nq, int64_t nk, int64_t d, float scale, const float* log_scale,
-                       const float* bias, int64_t diag_off) {
-    memset(&p, 0, sizeof(p));
-    p.s.Q = Q; p.s.K = K; p.s.nq = (int)nq; p.s.nk = (int)nk; p.s.d = (int)d; p.s.scale = scale; p.s.log_scale = log_scale;
-    p.s.diag_off = (int)diag_off;
-    p.s.tiles_m = (int)((nq + 127) / 128); p.s.tiles_n = (int)((nk + 127) / 128);
-    p.bias = bias;
-}
-
 int xclip_sigloss_partial(const void* Q, const void* K, int64_t nq, int64_t nk, int64_t d, float scale, const float* log_scale,
                           const float* bias, int64_t diag_off, void* workspace, int64_t tile_slot0, int64_t tile_slots, int dtype,
                           void* stream) {
-    XC_REQUIRE(dtype_ok(dtype), "bad dtype");
-    XC_REQUIRE(nq > 0 && nk > 0 && d > 0 && d % vec_of(dtype) == 0, "bad shape (d must be a multiple of the 16-byte chunk)");
-    XC_REQUIRE(aligned16(Q) && aligned16(K) && workspace != nullptr && bias != nullptr, "pointers must be 16-byte aligned / workspace and bias required");
-    XC_REQUIRE(nq < (1LL << 31) && nk < (1LL << 31) && diag_off > -(1LL << 31) && diag_off < (1LL << 31), "problem too large for 32-bit indices");
+    XC_SIM_REQUIRE(sim_bad_args(Q, K, nq, nk, d, diag_off, dtype));
+    XC_REQUIRE(workspace != nullptr && bias != nullptr, "workspace and bias required");
     XC_REQUIRE(tile_slot0 >= 0 && tile_slot0 + (nk + 63) / 64 <= tile_slots, "column slots out of range");
     SigParams p;
-    sig_params(p, Q, K, nq, nk, d, scale, log_scale, bias, diag_off);
+    memset(&p, 0, sizeof(p));
+    p.s = sim_params(Q, K, nq, nk, d, scale, log_scale, diag_off, 0);
+    p.bias = bias;
     p.part = (float*)workspace + tile_slot0 * nq;
-    hipStream_t st = (hipStream_t)stream;
-    if (use_sim3(nq, nk, d, dtype)) {
-        XC_ALLOW_LDS(sig5_loss_kernel, G5_LDS_BYTES);
-        hipLaunchKernelGGL(sig5_loss_kernel, sim3_grid(nq, nk), dim3(G2_THREADS), G5_LDS_BYTES, st, p);
-        return check_launch(__func__);
-    }
-    dim3 grid(p.s.tiles_m * p.s.tiles_n), block(256);
-    if (dtype == XCLIP_BF16) {
-        XC_ALLOW_LDS((sig_partial_kernel<bf16_t>), GemmCfg<bf16_t>::LDS_BYTES);
-        hipLaunchKernelGGL((sig_partial_kernel<bf16_t>), grid, block, GemmCfg<bf16_t>::LDS_BYTES, st, p);
-    } else {
-        XC_ALLOW_LDS((sig_partial_kernel<float>), GemmCfg<float>::LDS_BYTES);
-        hipLaunchKernelGGL((sig_partial_kernel<float>), grid, block, GemmCfg<float>::LDS_BYTES, st, p);
-    }
+    sim_launch<SigParams, sig5_loss_kernel, sig_partial_kernel<bf16_t>, sig_partial_kernel<float>>(p, p.s, dtype, (hipStream_t)stream);
     return check_launch(__func__);
 }
 
@@ -1541,118 +1561,59 @@ int xclip_sigloss_combine(const void* workspace, int64_t nq, int64_t tile_slots,
 int xclip_sigloss_grad(const void* Q, const void* K, int64_t nq, int64_t nk, int64_t d, float scale, const float* log_scale,
                        const float* bias, int64_t diag_off, float coef, const float* gmul, int g_times_scale, void* G, int64_t ldg,
                        float* dtau_accum, float* dbias_accum, int dtype, void* stream) {
-    XC_REQUIRE(dtype_ok(dtype), "bad dtype");
-    const int vec = vec_of(dtype);
-    XC_REQUIRE(nq > 0 && nk > 0 && d > 0 && d % vec == 0, "bad shape (d must be a multiple of the 16-byte chunk)");
-    XC_REQUIRE(ldg % vec == 0 && ldg >= (nk + vec - 1) / vec * vec, "ldg must cover nk rounded up to the chunk");
-    XC_REQUIRE(aligned16(Q) && aligned16(K) && aligned16(G) && bias != nullptr, "pointers must be 16-byte aligned / bias required");
-    XC_REQUIRE(nq < (1LL << 31) && nk < (1LL << 31) && diag_off > -(1LL << 31) && diag_off < (1LL << 31), "problem too large for 32-bit indices");
+    XC_SIM_REQUIRE(sim_bad_args(Q, K, nq, nk, d, diag_off, dtype));
+    XC_SIM_REQUIRE(sim_bad_g(G, ldg, nq, nk, d, dtype));
+    XC_REQUIRE(bias != nullptr, "bias required");
     SigParams p;
-    sig_params(p, Q, K, nq, nk, d, scale, log_scale, bias, diag_off);
+    memset(&p, 0, sizeof(p));
+    p.s = sim_params(Q, K, nq, nk, d, scale, log_scale, diag_off, 0);
     p.s.gmul = gmul; p.s.g_times_scale = g_times_scale; p.s.G = G; p.s.ldg = ldg; p.s.dtau = dtau_accum;
-    p.coef = coef; p.dbias = dbias_accum;
+    p.bias = bias; p.coef = coef; p.dbias = dbias_accum;
     hipStream_t st = (hipStream_t)stream;
-    if (use_sim3(nq, nk, d, dtype)) {
-        // every full 256 x 256 tile on the ring loop; tiles at a ragged edge, if there are any, through the general epilogue over a tile
-        // list in a second launch (xclip_simloss_grad)
-        XC_REQUIRE(255 * ldg * 2 + 512 < (1LL << 32), "ldg too large for the line stores");
-        if (nq >= G2_BM && nk >= G2_BN) {
-            if (nq * ldg * 2 > (48LL << 20)) {                      // G larger than the L2s can hold anyway: streamed stores
-                XC_ALLOW_LDS(sig5_grad_kernel<true>, G5_LDS_BYTES);
-                hipLaunchKernelGGL(sig5_grad_kernel<true>, sim3_grid(nq, nk), dim3(G2_THREADS), G5_LDS_BYTES, st, p);
-            } else {
-                XC_ALLOW_LDS(sig5_grad_kernel<false>, G5_LDS_BYTES);
-                hipLaunchKernelGGL(sig5_grad_kernel<false>, sim3_grid(nq, nk), dim3(G2_THREADS), G5_LDS_BYTES, st, p);
-            }
-        }
-        const int64_t tm = (nq + G2_BM - 1) / G2_BM, tn = (nk + G2_BN - 1) / G2_BN;
-        const int64_t nedge = ((nk % G2_BN) ? tm : 0) + ((nq % G2_BM) ? tn : 0);    // Sim5EdgeTiles::count
-        if (nedge == 0) return check_launch(__func__);
-        const int cus = xc_num_cus();
-        XC_ALLOW_LDS(sig5_grad_edge_kernel, G2_LDS_BYTES);
-        hipLaunchKernelGGL(sig5_grad_edge_kernel, dim3((unsigned)(nedge < cus ? nedge : cus)), dim3(G2_THREADS), G2_LDS_BYTES, st, p);
-        return check_launch(__func__);
-    }
-    dim3 grid(p.s.tiles_m * p.s.tiles_n), block(256);
-    if (dtype == XCLIP_BF16) {
-        XC_ALLOW_LDS((sig_grad_kernel<bf16_t>), GemmCfg<bf16_t>::LDS_BYTES);
-        hipLaunchKernelGGL((sig_grad_kernel<bf16_t>), grid, block, GemmCfg<bf16_t>::LDS_BYTES, st, p);
-    } else {
-        XC_ALLOW_LDS((sig_grad_kernel<float>), GemmCfg<float>::LDS_BYTES);
-        hipLaunchKernelGGL((sig_grad_kernel<float>), grid, block, GemmCfg<float>::LDS_BYTES, st, p);
-    }
+    if (use_sim3(nq, nk, d, dtype))
+        sim_launch_g<SigParams, sig5_grad_kernel<true>, sig5_grad_kernel<false>, sig5_grad_edge_kernel>(p, p.s, st);
+    else
+        sim_launch_general<SigParams, sig_grad_kernel<bf16_t>, sig_grad_kernel<float>>(p, p.s, dtype, st);
     return check_launch(__func__);
 }
 
 int xclip_simloss_grad(const void* Q, const void* K, int64_t nq, int64_t nk, int64_t d, float scale, const float* log_scale,
                        int64_t diag_off, int dcl, float a, float c, float e, const float* gmul, int g_times_scale,
                        const float* lse_q, const float* lse_k, void* G, int64_t ldg, float* dtau_accum, int dtype, void* stream) {
-    XC_REQUIRE(dtype_ok(dtype), "bad dtype");
-    const int vec = vec_of(dtype);
-    XC_REQUIRE(nq > 0 && nk > 0 && d > 0 && d % vec == 0, "bad shape (d must be a multiple of the 16-byte chunk)");
-    XC_REQUIRE(ldg % vec == 0 && ldg >= (nk + vec - 1) / vec * vec, "ldg must cover nk rounded up to the chunk");
-    XC_REQUIRE(aligned16(Q) && aligned16(K) && aligned16(G), "pointers must be 16-byte aligned");
-    SimParams p;
-    memset(&p, 0, sizeof(p));
-    p.Q = Q; p.K = K; p.nq = (int)nq; p.nk = (int)nk; p.d = (int)d; p.scale = scale; p.log_scale = log_scale;
-    p.gmul = gmul; p.g_times_scale = g_times_scale; p.diag_off = (int)diag_off; p.dcl = dcl;
-    p.tiles_m = (int)((nq + 127) / 128); p.tiles_n = (int)((nk + 127) / 128);
+    XC_SIM_REQUIRE(sim_bad_args(Q, K, nq, nk, d, diag_off, dtype));
+    XC_SIM_REQUIRE(sim_bad_g(G, ldg, nq, nk, d, dtype));
+    SimParams p = sim_params(Q, K, nq, nk, d, scale, log_scale, diag_off, dcl);
+    p.gmul = gmul; p.g_times_scale = g_times_scale;
     p.lse_q = lse_q; p.lse_k = lse_k; p.a = a; p.c = c; p.e = e; p.G = G; p.ldg = ldg; p.dtau = dtau_accum;
     hipStream_t st = (hipStream_t)stream;
-    if (use_sim3(nq, nk, d, dtype)) {
-        // simloss5.h: every full 256 x 256 tile (on the diagonal or off it) on the ring loop with a spill-free epilogue of its own; tiles at
-        // a ragged edge, if there are any, through simloss3.h's general epilogue over a tile list in a second launch.  XCLIP_SIM
-        // (measurement build): 3 = simloss3.h alone (one launch, every tile through the general epilogue: 355 - 368 us at
-        // 4096 x 32768 x 512), 5 = the first ring form (whole-line epilogue with the general tile in the same function: 423 us)
-#ifdef XCLIP_MEASURE
-        static const int gen = measure_env("XCLIP_SIM", 0);
-        if (gen == 5) {
-            XC_ALLOW_LDS(sim5_grad_kernel, G5_LDS_BYTES);
-            hipLaunchKernelGGL(sim5_grad_kernel, sim3_grid(nq, nk), dim3(G2_THREADS), G5_LDS_BYTES, st, p);
-            return check_launch(__func__);
-        }
-        if (gen == 3) {
-            XC_ALLOW_LDS(sim3_grad_kernel, G2_LDS_BYTES);
-            hipLaunchKernelGGL(sim3_grad_kernel, sim3_grid(nq, nk), dim3(G2_THREADS), G2_LDS_BYTES, st, p);
-            return check_launch(__func__);
-        }
-        // 7 = the full-tile launch alone, 8 = the edge launch alone (the split of the two)
-        const bool skip_fast = gen == 8, skip_edge = gen == 7;
-#else
-        const bool skip_fast = false, skip_edge = false;
-#endif
-#ifdef XCLIP_MEASURE
-        static const int simg = measure_env("XCLIP_SIMG", 0);      // A/B of this round's additions to the G kernel (simloss5.h VAR), streamed form only
-        if (!skip_fast && simg >= 1 && simg <= 4 && nq * ldg * 2 > (48LL << 20)) {
-#define XC_SIMG(V) case V: XC_ALLOW_LDS((sim5_grad_fast_kernel<true, V>), G5_LDS_BYTES); hipLaunchKernelGGL((sim5_grad_fast_kernel<true, V>), sim3_grid(nq, nk), dim3(G2_THREADS), G5_LDS_BYTES, st, p); break;
-            switch (simg) { XC_SIMG(1) XC_SIMG(2) XC_SIMG(3) XC_SIMG(4) }
-#undef XC_SIMG
-        } else
-#endif
-        if (skip_fast) {
-        } else if (nq * ldg * 2 > (48LL << 20)) {                   // G larger than the L2s can hold anyway: streamed stores
-            XC_ALLOW_LDS(sim5_grad_fast_kernel<true>, G5_LDS_BYTES);
-            hipLaunchKernelGGL(sim5_grad_fast_kernel<true>, sim3_grid(nq, nk), dim3(G2_THREADS), G5_LDS_BYTES, st, p);
-        } else {
-            XC_ALLOW_LDS(sim5_grad_fast_kernel<false>, G5_LDS_BYTES);
-            hipLaunchKernelGGL(sim5_grad_fast_kernel<false>, sim3_grid(nq, nk), dim3(G2_THREADS), G5_LDS_BYTES, st, p);
-        }
-        const int64_t tm = (nq + G2_BM - 1) / G2_BM, tn = (nk + G2_BN - 1) / G2_BN;
-        const int64_t nedge = ((nk % G2_BN) ? tm : 0) + ((nq % G2_BM) ? tn : 0);    // Sim5EdgeTiles::count
-        if (skip_edge || nedge == 0) return check_launch(__func__);
-        const int cus = xc_num_cus();
-        XC_ALLOW_LDS(sim5_grad_edge_kernel, G2_LDS_BYTES);
-        hipLaunchKernelGGL(sim5_grad_edge_kernel, dim3((unsigned)(nedge < cus ? nedge : cus)), dim3(G2_THREADS), G2_LDS_BYTES, st, p);
+    if (!use_sim3(nq, nk, d, dtype)) {
+        sim_launch_general<SimParams, sim_grad_kernel<bf16_t>, sim_grad_kernel<float>>(p, p, dtype, st);
         return check_launch(__func__);
     }
-    dim3 grid(p.tiles_m * p.tiles_n), block(256);
-    if (dtype == XCLIP_BF16) {
-        XC_ALLOW_LDS((sim_grad_kernel<bf16_t>), GemmCfg<bf16_t>::LDS_BYTES);
-        hipLaunchKernelGGL((sim_grad_kernel<bf16_t>), grid, block, GemmCfg<bf16_t>::LDS_BYTES, st, p);
-    } else {
-        XC_ALLOW_LDS((sim_grad_kernel<float>), GemmCfg<float>::LDS_BYTES);
-        hipLaunchKernelGGL((sim_grad_kernel<float>), grid, block, GemmCfg<float>::LDS_BYTES, st, p);
+    // XCLIP_SIM (measurement build): 3 = simloss3.h alone (one launch, every tile through the general epilogue: 355 - 368 us at
+    // 4096 x 32768 x 512), 5 = the first ring form (whole-line epilogue with the general tile in the same function: 423 us),
+    // 7 = the full-tile launch alone, 8 = the edge launch alone (the split of the two)
+    bool without_full = false, without_edge = false;
+#ifdef XCLIP_MEASURE
+    static const int gen = measure_env("XCLIP_SIM", 0);
+    if (gen == 5) {
+        XC_ALLOW_LDS(sim5_grad_kernel, G5_LDS_BYTES);
+        hipLaunchKernelGGL(sim5_grad_kernel, sim3_grid(nq, nk), dim3(G2_THREADS), G5_LDS_BYTES, st, p);
+        return check_launch(__func__);
     }
+    if (gen == 3) {
+        XC_ALLOW_LDS(sim3_grad_kernel, G2_LDS_BYTES);
+        hipLaunchKernelGGL(sim3_grad_kernel, sim3_grid(nq, nk), dim3(G2_THREADS), G2_LDS_BYTES, st, p);
+        return check_launch(__func__);
+    }
+    without_full = gen == 8;
+    without_edge = gen == 7;
+    static const int simg = measure_env("XCLIP_SIMG", 0);      // A/B of the additions to the G kernel (simloss5.h VAR), streamed form only
+#define XC_SIMG(V) case V: sim_launch_g<SimParams, sim5_grad_fast_kernel<true, V>, sim5_grad_fast_kernel<false>, sim5_grad_edge_kernel>(p, p, st, without_full, without_edge); return check_launch(__func__);
+    switch (simg) { XC_SIMG(1) XC_SIMG(2) XC_SIMG(3) XC_SIMG(4) }
+#undef XC_SIMG
+#endif
+    sim_launch_g<SimParams, sim5_grad_fast_kernel<true>, sim5_grad_fast_kernel<false>, sim5_grad_edge_kernel>(p, p, st, without_full, without_edge);
     return check_launch(__func__);
 }
 

@@ -50,12 +50,22 @@ def _acc_gemm(acc: Optional[Tensor], a: Tensor, b: Tensor, M: int, N: int, K: in
 
 def _exchange(spec: ContrastiveSpec, mats, b: int, dev):
     """cross-rank exchange of the latent views (x_clip.py:759-769) -> sizes, rank, first global row of this rank, global batch,
-    {name: GatheredViews} (empty in a single process)"""
+    {name: GatheredViews} (empty in a single process, or with mats = {}: the geometry alone)"""
     if not spec.distributed:
         return [b], 0, 0, b, {}
     sizes = [b] * xdist.dist.get_world_size(spec.group) if spec.assume_equal_batch else xdist.exchange_sizes(b, dev, spec.group)
     rank = xdist.dist.get_rank(spec.group)
     return sizes, rank, sum(sizes[:rank]), sum(sizes), {name: xdist.GatheredViews(views, sizes, spec.group) for name, views in mats.items()}
+
+
+def _pair_weight(spec: ContrastiveSpec, i: int, j: int, npairs: int) -> float:
+    """the loss weight of view pair (i, j): the main pair, or an equal share of the multiview weight (x_clip.py:851-868)"""
+    return spec.main_weight if (i, j) == (0, 0) else spec.multiview_weight / max(npairs - 1, 1)
+
+
+def _waiter(gathered):
+    """-> the before_chunk hook of a chunked head over gathered.chunks(): the local chunk, first in line, needs no all-gather"""
+    return lambda c: gathered.wait() if c == 1 else None
 
 
 def _column_chunks(spec: ContrastiveSpec, mats, gathered, name: str, view: int, sizes, rank: int, v: int):
@@ -82,6 +92,22 @@ def _stack_views(grads, b: int, d: int, dt, dev) -> Tensor:
     return out
 
 
+def _g_block(spec: ContrastiveSpec, mats, gathered, grads, qn: str, qv: int, kn: str, kv: int, geom, grad_chunk) -> Tensor:
+    """G for the local rows of mats[qn][qv] against every column chunk of kn/kv, then dQ += G K (both backward passes).
+    geom = (b, d, B, off, sizes, rank); grad_chunk(Q, K, diag_off, r, out): the head's G kernel for one chunk (r: _column_chunks)"""
+    b, d, B, off, sizes, rank = geom
+    Q = mats[qn][qv]
+    v = ops.vec(Q.dtype)
+    G = torch.empty(b, (B + v - 1) // v * v, dtype=Q.dtype, device=Q.device)
+    chunks, order = _column_chunks(spec, mats, gathered, kn, kv, sizes, rank, v)
+    for (K, col0), r in zip(chunks, order):
+        if K.shape[0] == 0:                     # a peer without rows
+            continue
+        grad_chunk(Q, K, off - col0, r, G[:, col0: col0 + (K.shape[0] + v - 1) // v * v])
+        grads[qn][qv] = _acc_gemm(grads[qn][qv], G[:, col0: col0 + K.shape[0]], K, b, d, K.shape[0], a_kmajor=False)
+    return G
+
+
 class _ContrastiveFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, spec: ContrastiveSpec, tau: Tensor, T: Tensor, I: Tensor, Tx: Optional[Tensor], Ix: Optional[Tensor]):
@@ -100,7 +126,7 @@ class _ContrastiveFn(torch.autograd.Function):
             return gathered[name].chunks(v) if spec.distributed else [(mats[name][v], 0)]
 
         def waiter(name):
-            return (lambda c: gathered[name].wait() if c == 1 else None) if spec.distributed else None
+            return _waiter(gathered[name]) if spec.distributed else None
 
         # (X name, Y name, X view of pair (i, j), Y view of pair (i, j), cx, cy):  rows of X against all of Y
         groups = [("T", "I", lambda i, j: i, lambda i, j: j, 1.0, 0.0), ("Ix", "Tx", lambda i, j: j, lambda i, j: i, 1.0, 0.0)] \
@@ -112,7 +138,7 @@ class _ContrastiveFn(torch.autograd.Function):
         for gi, (xn, yn, xv, yv, cx, cy) in enumerate(groups):
             for i in range(m):
                 for j in range(n):
-                    w = spec.main_weight if (i == 0 and j == 0) else spec.multiview_weight / max(npairs - 1, 1)
+                    w = _pair_weight(spec, i, j, npairs)
                     coef_x, coef_y = cx * w / (2.0 * B), cy * w / (2.0 * B)
                     ix = iy = -1
                     if coef_x != 0.0:
@@ -156,7 +182,6 @@ class _ContrastiveFn(torch.autograd.Function):
         m, n, b, d, B, off, sizes, rank, extra, tau_dtype = ctx.geom
         dev = tau32.device
         dt = mats["T"][0].dtype
-        v = ops.vec(dt)
         gmul = dloss.detach().reshape(1).float().contiguous()
         dtau = torch.zeros(1, dtype=torch.float32, device=dev)
         grads = {name: [None] * len(views) for name, views in mats.items()}
@@ -165,28 +190,19 @@ class _ContrastiveFn(torch.autograd.Function):
             return lse_all[r, idx, : sizes[r]] if spec.distributed else lse_local[idx]
 
         def block(qn, qv, kn, kv, a, c, lse_q_idx, lse_k_idx, want_dtau):
-            """G for the local rows of mats[qn][qv] against every column chunk of kn/kv, then dQ += G K."""
-            Q = mats[qn][qv]
-            ldg = (B + v - 1) // v * v
-            G = torch.empty(b, ldg, dtype=dt, device=dev)
-            chunks, order = _column_chunks(spec, mats, gathered, kn, kv, sizes, rank, v)
-            zero_q = None
-            for (K, col0), r in zip(chunks, order):
-                if lse_q_idx >= 0:
-                    lq = lse_local[lse_q_idx]
-                else:
-                    zero_q = zero_q if zero_q is not None else torch.zeros(b, dtype=torch.float32, device=dev)
-                    lq = zero_q
+            lq = lse_local[lse_q_idx] if lse_q_idx >= 0 else torch.zeros(b, dtype=torch.float32, device=dev)
+
+            def grad_chunk(Q, K, diag_off, r, out):
                 if lse_k_idx < 0:
                     lk = torch.zeros(K.shape[0], dtype=torch.float32, device=dev)
                 elif r is None:
                     lk = torch.cat([lse_chunk(lse_k_idx, q) for q in range(len(sizes))])
                 else:
                     lk = lse_chunk(lse_k_idx, r)
-                ops.simloss_grad(Q, K, 1.0, off - col0, spec.dcl, a, c, a + c, lq, ops._c(lk), dtau if want_dtau else None,
-                                 log_scale=tau32, gmul=gmul, times_scale=True, out=G[:, col0: col0 + (K.shape[0] + v - 1) // v * v])
-                grads[qn][qv] = _acc_gemm(grads[qn][qv], G[:, col0: col0 + K.shape[0]], K, b, d, K.shape[0], a_kmajor=False)
-            return G
+                ops.simloss_grad(Q, K, 1.0, diag_off, spec.dcl, a, c, a + c, lq, ops._c(lk), dtau if want_dtau else None,
+                                 log_scale=tau32, gmul=gmul, times_scale=True, out=out)
+
+            return _g_block(spec, mats, gathered, grads, qn, qv, kn, kv, (b, d, B, off, sizes, rank), grad_chunk)
 
         for (gi, i, j, coef_x, coef_y, ix, iy) in plan:
             xn, yn, xv, yv, _, _ = groups[gi]
@@ -245,12 +261,11 @@ class _SigmoidFn(torch.autograd.Function):
         plan = []                                 # (i, j, coef)
         for i in range(m):
             for j in range(n):
-                w = spec.main_weight if (i == 0 and j == 0) else spec.multiview_weight / max(npairs - 1, 1)
-                coef = w / B
+                coef = _pair_weight(spec, i, j, npairs) / B
                 if coef != 0.0:
                     ops.sigloss_chunked_fwd(mats["T"][i], gathered["I"].chunks(j) if spec.distributed else [(mats["I"][j], 0)], 1.0, off,
                                             coef, loss, log_scale=tau32, bias=bias32,
-                                            before_chunk=(lambda c: gathered["I"].wait() if c == 1 else None) if spec.distributed else None)
+                                            before_chunk=_waiter(gathered["I"]) if spec.distributed else None)
                     plan.append((i, j, coef))
         if spec.distributed:
             for g in gathered.values():
@@ -269,26 +284,17 @@ class _SigmoidFn(torch.autograd.Function):
         m, n, b, d, B, off, sizes, rank, tau_dtype, bias_dtype = ctx.geom
         dev = tau32.device
         dt = mats["T"][0].dtype
-        v = ops.vec(dt)
         gmul = dloss.detach().reshape(1).float().contiguous()
         dtau = torch.zeros(1, dtype=torch.float32, device=dev)
         dbias = torch.zeros(1, dtype=torch.float32, device=dev)
         grads = {name: [None] * len(views) for name, views in mats.items()}
 
         def block(qn, qv, kn, kv, coef, want_acc):
-            """G for the local rows of mats[qn][qv] against every column chunk of kn/kv, then dQ += G K."""
-            Q = mats[qn][qv]
-            ldg = (B + v - 1) // v * v
-            G = torch.empty(b, ldg, dtype=dt, device=dev)
-            chunks, _ = _column_chunks(spec, mats, gathered, kn, kv, sizes, rank, v)
-            for K, col0 in chunks:
-                if K.shape[0] == 0:                 # a peer without rows
-                    continue
-                ops.sigloss_grad(Q, K, 1.0, off - col0, coef, dtau if want_acc else None, dbias if want_acc else None,
-                                 log_scale=tau32, bias=bias32, gmul=gmul, times_scale=True,
-                                 out=G[:, col0: col0 + (K.shape[0] + v - 1) // v * v])
-                grads[qn][qv] = _acc_gemm(grads[qn][qv], G[:, col0: col0 + K.shape[0]], K, b, d, K.shape[0], a_kmajor=False)
-            return G
+            def grad_chunk(Q, K, diag_off, r, out):
+                ops.sigloss_grad(Q, K, 1.0, diag_off, coef, dtau if want_acc else None, dbias if want_acc else None,
+                                 log_scale=tau32, bias=bias32, gmul=gmul, times_scale=True, out=out)
+
+            return _g_block(spec, mats, gathered, grads, qn, qv, kn, kv, (b, d, B, off, sizes, rank), grad_chunk)
 
         for (i, j, coef) in (plan if b > 0 else []):    # a rank without rows launches nothing
             # block A: local T rows vs all I  ->  dT (and, single process, dI through G^T)
@@ -335,14 +341,11 @@ class _SimRegFn(torch.autograd.Function):
         b, d = T.shape
         v = ops.vec(dt)
         mats = [ops._c(x.detach()) for x in (T, I, Tx, Ix)]
+        sizes, _, off, B, _ = _exchange(spec, {}, b, dev)
+        gathered = None
         if spec.distributed:
-            sizes = [b] * xdist.dist.get_world_size(spec.group) if spec.assume_equal_batch else xdist.exchange_sizes(b, dev, spec.group)
-            rank = xdist.dist.get_rank(spec.group)
-            off, B = sum(sizes[:rank]), sum(sizes)
             gathered = xdist.GatheredViews(mats, sizes, spec.group)
             gathered.wait()
-        else:
-            off, B, gathered = 0, b, None
         Bp = (B + v - 1) // v * v                              # GEMM N / K must be whole 16-byte chunks: zero rows contribute nothing
         alls = []
         for k in range(4):
@@ -520,12 +523,7 @@ class _FilipFn(torch.autograd.Function):
         extra = Tx is not None
         tau32 = tau.detach().reshape(1).float().contiguous()
         mask_u8 = mask.reshape(m, b, nt).to(torch.uint8).contiguous()
-        if spec.distributed:
-            sizes = [b] * xdist.dist.get_world_size(spec.group) if spec.assume_equal_batch else xdist.exchange_sizes(b, dev, spec.group)
-            rank = xdist.dist.get_rank(spec.group)
-            off, B = sum(sizes[:rank]), sum(sizes)
-        else:
-            sizes, rank, off, B = [b], 0, 0, b
+        sizes, _, off, B, _ = _exchange(spec, {}, b, dev)
 
         def everyone(t):                                 # [b, ...] -> [B, ...]
             return _gather_rows(ops._c(t), sizes, spec.group) if spec.distributed else ops._c(t)
@@ -539,8 +537,7 @@ class _FilipFn(torch.autograd.Function):
         blocks = []
         for i in range(m):
             for j in range(n):
-                w = spec.main_weight if (i == 0 and j == 0) else spec.multiview_weight / max(npairs - 1, 1)
-                coef = w / (2.0 * B)
+                coef = _pair_weight(spec, i, j, npairs) / (2.0 * B)
                 blk1 = _FilipBlock(Ts[i], mask_u8[i], Is_all[j], tau32).forward()
                 blk2 = _FilipBlock(Txs[i], mask_u8[i], Ixs_all[j], tau32).forward() if extra else blk1
                 lse1 = ops.rowlse(blk1.t2i, off, spec.dcl, coef, loss)

@@ -16,6 +16,7 @@ import torch
 
 from . import distributed as xdist
 from . import ops
+from .losses import _waiter
 
 Tensor = torch.Tensor
 
@@ -74,8 +75,8 @@ def contrastive_metrics(text_latents: Tensor, image_latents: Tensor, temperature
             raise ValueError(f"contrastive_metrics: {Bt} texts and {Bi} images over all ranks -- in-batch retrieval needs matched pairs")
         gt, gi = xdist.GatheredViews([T], tsizes, group, tag="metrics_gather"), xdist.GatheredViews([I], isizes, group, tag="metrics_gather")
         toff, ioff = sum(tsizes[:rk]), sum(isizes[:rk])
-        t2i, s1 = _direction(T, gi.chunks(0), toff, tau32, ks, lambda c: gi.wait() if c == 1 else None)
-        i2t, s2 = _direction(I, gt.chunks(0), ioff, tau32, ks, lambda c: gt.wait() if c == 1 else None)
+        t2i, s1 = _direction(T, gi.chunks(0), toff, tau32, ks, _waiter(gi))
+        i2t, s2 = _direction(I, gt.chunks(0), ioff, tau32, ks, _waiter(gt))
         gi.wait()
         gt.wait()
         sums = xdist.all_reduce_scalars(torch.stack([s1, s2]), group)

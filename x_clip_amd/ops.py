@@ -761,6 +761,42 @@ def simloss_fwd(q: Tensor, k: Tensor, scale: float, diag_off: int, dcl: bool, co
     return simloss_chunked_fwd(q, [(k, 0)], scale, diag_off, dcl, coef, loss_accum, log_scale)
 
 
+def _chunked_head(q: Tensor, k_chunks, before_chunk, per_slot: int, partial, combine, label: str, neutral=None, stage=None,
+                  extra_bytes: int = 0):
+    """The chunk loop under simloss_chunked_fwd / simrank_chunked / sigloss_chunked_fwd: one workspace of `per_slot` 4-byte partials per
+    (row, 64-column slot) over all chunks, `before_chunk(c)` once per chunk, in order, before that chunk is touched, `partial(kc, col0,
+    slot0, slots, ws)` per chunk under the kernel probe (`label`), then `combine(ws, slots)`.
+    `neutral` (a callable or None): the head takes empty inputs -- chunks without rows are skipped, and a call without rows or without
+    any column launches nothing and returns neutral(); the hooks still run, so a pending all-gather is waited for as usual.  None: empty
+    inputs go to the C layer, which refuses them.
+    `stage(kc, col0, slot0)` -> the (kc, col0, slot0) to sweep now: lets a head hold chunks back (None: each chunk as it comes)."""
+    nq, d = q.shape
+    slots = sum((kc.shape[0] + 63) // 64 for kc, _ in k_chunks)
+    if neutral is not None and (nq == 0 or slots == 0):
+        for c in range(len(k_chunks) if before_chunk is not None else 0):
+            before_chunk(c)
+        return neutral()
+    ws = workspace(q.device, per_slot * slots * nq * 4)
+    slot0 = 0
+    for c, (kc, col0) in enumerate(k_chunks):
+        if before_chunk is not None:
+            before_chunk(c)
+        kc = _c(kc)
+        nk = kc.shape[0]
+        assert kc.shape[1] == d and kc.dtype == q.dtype
+        if nk == 0 and neutral is not None:                         # a peer without rows: no columns, no slots
+            continue
+        for kc, col0, s0 in ([(kc, col0, slot0)] if stage is None else stage(kc, col0, slot0)):
+            probe = _probe(q)
+            ev0 = probe.begin(q) if probe is not None else None
+            partial(kc, col0, s0, slots, ws)
+            if probe is not None:  # S = q k^T once; both latent sets (and extra_bytes) in, per_slot 4-byte partials per (row, slot) out
+                probe.end(q, ev0, "head", 2.0 * nq * kc.shape[0] * d,
+                          (nq + kc.shape[0]) * d * q.element_size() + extra_bytes + 4 * per_slot * nq * ((kc.shape[0] + 63) // 64), label)
+        slot0 += (nk + 63) // 64
+    return combine(ws, slots)
+
+
 def simloss_chunked_fwd(q: Tensor, k_chunks, scale: float, diag_off: int, dcl: bool, coef: float, loss_accum: Optional[Tensor],
                         log_scale: Optional[Tensor] = None, before_chunk=None):
     """Same result as simloss_fwd(q, K) with K given as a list of (chunk [nk_c, d], first global column) in the order they
@@ -770,27 +806,19 @@ def simloss_chunked_fwd(q: Tensor, k_chunks, scale: float, diag_off: int, dcl: b
     nq, d = q.shape
     L = _lib.lib()
     sc, lsp = _scale_args(scale, log_scale)
-    slots = sum((kc.shape[0] + 63) // 64 for kc, _ in k_chunks)
-    ws = workspace(q.device, 2 * slots * nq * 4)
     pos = torch.zeros(nq, dtype=torch.float32, device=q.device)
     lse = torch.empty(nq, dtype=torch.float32, device=q.device)
-    slot0 = 0
-    for c, (kc, col0) in enumerate(k_chunks):
-        if before_chunk is not None:
-            before_chunk(c)
-        kc = _c(kc)
-        nk = kc.shape[0]
-        assert kc.shape[1] == d and kc.dtype == q.dtype
-        probe = _probe(q)
-        ev0 = probe.begin(q) if probe is not None else None
-        _lib.check(L.xclip_simloss_partial(q.data_ptr(), kc.data_ptr(), nq, nk, d, sc, lsp, diag_off - col0, int(dcl), ws.data_ptr(),
+
+    def partial(kc, col0, slot0, slots, ws):
+        _lib.check(L.xclip_simloss_partial(q.data_ptr(), kc.data_ptr(), nq, kc.shape[0], d, sc, lsp, diag_off - col0, int(dcl), ws.data_ptr(),
                                            slot0, slots, pos.data_ptr(), dtype_code(q), _stream(q)), "xclip_simloss_partial")
-        if probe is not None:      # S = q k^T once; both latent sets in, two fp32 partials per (row, 64-column slot) out
-            probe.end(q, ev0, "head", 2.0 * nq * nk * d, (nq + nk) * d * q.element_size() + 8 * nq * ((nk + 63) // 64), "sim_fwd")
-        slot0 += (nk + 63) // 64
-    _lib.check(L.xclip_simloss_combine(ws.data_ptr(), nq, slots, pos.data_ptr(), lse.data_ptr(), _ptr(loss_accum), coef, _stream(q)),
-               "xclip_simloss_combine")
-    return lse, pos
+
+    def combine(ws, slots):
+        _lib.check(L.xclip_simloss_combine(ws.data_ptr(), nq, slots, pos.data_ptr(), lse.data_ptr(), _ptr(loss_accum), coef, _stream(q)),
+                   "xclip_simloss_combine")
+        return lse, pos
+
+    return _chunked_head(q, k_chunks, before_chunk, 2, partial, combine, "sim_fwd")
 
 
 def simrank(q: Tensor, k: Tensor, scale: float, diag_off: int, log_scale: Optional[Tensor] = None, thr: Optional[Tensor] = None):
@@ -809,19 +837,6 @@ def simrank_chunked(q: Tensor, k_chunks, scale: float, diag_off: int, log_scale:
     nq, d = q.shape
     L = _lib.lib()
     sc, lsp = _scale_args(scale, log_scale)
-    slots = sum((kc.shape[0] + 63) // 64 for kc, _ in k_chunks)
-    if nq == 0 or slots == 0:
-        # a rank without rows (or nothing to score against) launches nothing: every row has rank 0 and no hardest negative.  The
-        # hooks still run, so a pending all-gather is waited for as usual
-        for c in range(len(k_chunks) if before_chunk is not None else 0):
-            before_chunk(c)
-        return (torch.zeros(nq, dtype=torch.int32, device=q.device), torch.full((nq,), -3.0e38, dtype=torch.float32, device=q.device),
-                torch.full((nq,), -1, dtype=torch.int32, device=q.device),
-                torch.zeros(nq, dtype=torch.float32, device=q.device) if thr is None else thr)
-    ws = workspace(q.device, 3 * slots * nq * 4)
-    rank = torch.empty(nq, dtype=torch.int32, device=q.device)
-    hard_val = torch.empty(nq, dtype=torch.float32, device=q.device)
-    hard_idx = torch.empty(nq, dtype=torch.int32, device=q.device)
     code, st = dtype_code(q), _stream(q)
     own_thr = thr is None
     if own_thr:
@@ -829,41 +844,58 @@ def simrank_chunked(q: Tensor, k_chunks, scale: float, diag_off: int, log_scale:
     else:
         assert thr.dtype == torch.float32 and thr.numel() == nq and thr.is_contiguous()
 
+    def neutral():                                                  # every row has rank 0 and no hardest negative
+        return (torch.zeros(nq, dtype=torch.int32, device=q.device), torch.full((nq,), -3.0e38, dtype=torch.float32, device=q.device),
+                torch.full((nq,), -1, dtype=torch.int32, device=q.device), thr)
+
     def positives_in(nk, col0):                                     # rows of q whose positive lies in columns [col0, col0 + nk)
         return max(0, min(diag_off + nq, col0 + nk) - max(diag_off, col0))
 
     # a chunk's sweep needs every row's threshold, whichever chunk holds that row's positive: sweeps wait until the chunks seen so far
     # hold all the positives there are (the local chunk, first in line, holds them all when both sides are batched alike)
     missing = sum(positives_in(kc.shape[0], col0) for kc, col0 in k_chunks) if own_thr else 0
-    pending, slot0 = [], 0
-    for c, (kc, col0) in enumerate(k_chunks):
-        if before_chunk is not None:
-            before_chunk(c)
-        kc = _c(kc)
+    pending = []
+
+    def stage(kc, col0, slot0):
+        nonlocal missing, pending
         nk = kc.shape[0]
-        assert kc.shape[1] == d and kc.dtype == q.dtype
-        if nk == 0:                                                 # a peer without rows: no columns, no slots
-            continue
         if own_thr and positives_in(nk, col0) > 0:
             _lib.check(L.xclip_simrank_pos(q.data_ptr(), kc.data_ptr(), nq, nk, d, sc, lsp, diag_off - col0, thr.data_ptr(), code, st),
                        "xclip_simrank_pos")
             missing -= positives_in(nk, col0)
         pending.append((kc, col0, slot0))
-        slot0 += (nk + 63) // 64
         if missing > 0:
-            continue
-        for kc, col0, s0 in pending:
-            nk = kc.shape[0]
-            probe = _probe(q)
-            ev0 = probe.begin(q) if probe is not None else None
-            _lib.check(L.xclip_simrank_partial(q.data_ptr(), kc.data_ptr(), nq, nk, d, sc, lsp, diag_off - col0, col0, thr.data_ptr(),
-                                               ws.data_ptr(), s0, slots, code, st), "xclip_simrank_partial")
-            if probe is not None:  # S = q k^T once; both latent sets and the thresholds in, three 4-byte partials per (row, slot) out
-                probe.end(q, ev0, "head", 2.0 * nq * nk * d, (nq + nk) * d * q.element_size() + 4 * nq + 12 * nq * ((nk + 63) // 64), "sim_rank")
-        pending = []
-    _lib.check(L.xclip_simrank_combine(ws.data_ptr(), nq, slots, rank.data_ptr(), hard_val.data_ptr(), hard_idx.data_ptr(), st),
-               "xclip_simrank_combine")
-    return rank, hard_val, hard_idx, thr
+            return []
+        ready, pending = pending, []
+        return ready
+
+    def partial(kc, col0, slot0, slots, ws):
+        _lib.check(L.xclip_simrank_partial(q.data_ptr(), kc.data_ptr(), nq, kc.shape[0], d, sc, lsp, diag_off - col0, col0, thr.data_ptr(),
+                                           ws.data_ptr(), slot0, slots, code, st), "xclip_simrank_partial")
+
+    def combine(ws, slots):
+        rank = torch.empty(nq, dtype=torch.int32, device=q.device)
+        hard_val = torch.empty(nq, dtype=torch.float32, device=q.device)
+        hard_idx = torch.empty(nq, dtype=torch.int32, device=q.device)
+        _lib.check(L.xclip_simrank_combine(ws.data_ptr(), nq, slots, rank.data_ptr(), hard_val.data_ptr(), hard_idx.data_ptr(), st),
+                   "xclip_simrank_combine")
+        return rank, hard_val, hard_idx, thr
+
+    # (extra_bytes: the thresholds)
+    return _chunked_head(q, k_chunks, before_chunk, 3, partial, combine, "sim_rank", neutral=neutral, stage=stage, extra_bytes=4 * nq)
+
+
+def _g_out(q: Tensor, nk: int, out: Optional[Tensor], gmul: Optional[Tensor]):
+    """-> G [nq, nk rounded up to the chunk] in q.dtype for a grad (`out` checked, or a new tensor) and its row length"""
+    v = vec(q.dtype)
+    ldg = (nk + v - 1) // v * v
+    if out is None:
+        out = torch.empty(q.shape[0], ldg, dtype=q.dtype, device=q.device)
+    else:
+        assert out.dim() == 2 and out.stride(1) == 1 and out.shape[0] == q.shape[0] and out.shape[1] >= ldg and out.dtype == q.dtype
+    if gmul is not None:
+        assert gmul.dtype == torch.float32 and gmul.numel() == 1
+    return out, ldg
 
 
 def simloss_grad(q: Tensor, k: Tensor, scale: float, diag_off: int, dcl: bool, a: float, c: float, e: float, lse_q: Tensor,
@@ -875,17 +907,9 @@ def simloss_grad(q: Tensor, k: Tensor, scale: float, diag_off: int, dcl: bool, a
     q, k = _c(q), _c(k)
     nq, d = q.shape
     nk = k.shape[0]
-    v = vec(q.dtype)
-    ldg = (nk + v - 1) // v * v
-    if out is None:
-        G = torch.empty(nq, ldg, dtype=q.dtype, device=q.device)
-    else:
-        G = out
-        assert G.dim() == 2 and G.stride(1) == 1 and G.shape[0] == nq and G.shape[1] >= ldg and G.dtype == q.dtype
+    G, ldg = _g_out(q, nk, out, gmul)
     assert lse_q.dtype == torch.float32 and lse_k.dtype == torch.float32 and lse_q.numel() == nq and lse_k.numel() == nk
     assert lse_q.is_contiguous() and lse_k.is_contiguous()
-    if gmul is not None:
-        assert gmul.dtype == torch.float32 and gmul.numel() == 1
     sc, lsp = _scale_args(scale, log_scale)
     probe = _probe(q)
     ev0 = probe.begin(q) if probe is not None else None
@@ -924,33 +948,21 @@ def sigloss_chunked_fwd(q: Tensor, k_chunks, scale: float, diag_off: int, coef: 
     bp = _bias_arg(bias)
     if out is not None:
         assert out.dtype == torch.float32 and out.shape == (nq,) and out.is_contiguous()
-    slots = sum((kc.shape[0] + 63) // 64 for kc, _ in k_chunks)
-    if nq == 0 or slots == 0:
-        # a rank without rows (or nothing to score against) launches nothing; the hooks still run, so a pending all-gather is waited for
-        for c in range(len(k_chunks) if before_chunk is not None else 0):
-            before_chunk(c)
+
+    def neutral():
         return torch.zeros(nq, dtype=torch.float32, device=q.device) if out is None else out.zero_()
-    ws = workspace(q.device, slots * nq * 4)
-    rowloss = torch.empty(nq, dtype=torch.float32, device=q.device) if out is None else out
-    slot0 = 0
-    for c, (kc, col0) in enumerate(k_chunks):
-        if before_chunk is not None:
-            before_chunk(c)
-        kc = _c(kc)
-        nk = kc.shape[0]
-        assert kc.shape[1] == d and kc.dtype == q.dtype
-        if nk == 0:                                                 # a peer without rows: no columns, no slots
-            continue
-        probe = _probe(q)
-        ev0 = probe.begin(q) if probe is not None else None
-        _lib.check(L.xclip_sigloss_partial(q.data_ptr(), kc.data_ptr(), nq, nk, d, sc, lsp, bp, diag_off - col0, ws.data_ptr(), slot0, slots,
-                                           dtype_code(q), _stream(q)), "xclip_sigloss_partial")
-        if probe is not None:      # S = q k^T once; both latent sets in, one fp32 partial per (row, 64-column slot) out
-            probe.end(q, ev0, "head", 2.0 * nq * nk * d, (nq + nk) * d * q.element_size() + 4 * nq * ((nk + 63) // 64), "sig_fwd")
-        slot0 += (nk + 63) // 64
-    _lib.check(L.xclip_sigloss_combine(ws.data_ptr(), nq, slots, rowloss.data_ptr(), _ptr(loss_accum), coef, _stream(q)),
-               "xclip_sigloss_combine")
-    return rowloss
+
+    def partial(kc, col0, slot0, slots, ws):
+        _lib.check(L.xclip_sigloss_partial(q.data_ptr(), kc.data_ptr(), nq, kc.shape[0], d, sc, lsp, bp, diag_off - col0, ws.data_ptr(), slot0,
+                                           slots, dtype_code(q), _stream(q)), "xclip_sigloss_partial")
+
+    def combine(ws, slots):
+        rowloss = torch.empty(nq, dtype=torch.float32, device=q.device) if out is None else out
+        _lib.check(L.xclip_sigloss_combine(ws.data_ptr(), nq, slots, rowloss.data_ptr(), _ptr(loss_accum), coef, _stream(q)),
+                   "xclip_sigloss_combine")
+        return rowloss
+
+    return _chunked_head(q, k_chunks, before_chunk, 1, partial, combine, "sig_fwd", neutral=neutral)
 
 
 def sigloss_grad(q: Tensor, k: Tensor, scale: float, diag_off: int, coef: float, dtau_accum: Optional[Tensor],
@@ -962,15 +974,7 @@ def sigloss_grad(q: Tensor, k: Tensor, scale: float, diag_off: int, coef: float,
     q, k = _c(q), _c(k)
     nq, d = q.shape
     nk = k.shape[0]
-    v = vec(q.dtype)
-    ldg = (nk + v - 1) // v * v
-    if out is None:
-        G = torch.empty(nq, ldg, dtype=q.dtype, device=q.device)
-    else:
-        G = out
-        assert G.dim() == 2 and G.stride(1) == 1 and G.shape[0] == nq and G.shape[1] >= ldg and G.dtype == q.dtype
-    if gmul is not None:
-        assert gmul.dtype == torch.float32 and gmul.numel() == 1
+    G, ldg = _g_out(q, nk, out, gmul)
     sc, lsp = _scale_args(scale, log_scale)
     bp = _bias_arg(bias)
     if nq == 0 or nk == 0:                                          # a rank / a peer without rows: nothing to launch
