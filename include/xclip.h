@@ -20,7 +20,7 @@ extern "C" {
 #endif
 
 enum { XCLIP_F32 = 0, XCLIP_BF16 = 1 };
-#define XCLIP_ABI_VERSION 26
+#define XCLIP_ABI_VERSION 27
 
 int xclip_abi_version(void);
 const char* xclip_last_error(void);
@@ -94,7 +94,7 @@ int xclip_token_mean_bwd(const void* dout, const void* dsrc, int64_t src_batch_s
 int xclip_copy_rows(const void* src, int64_t lds, void* dst, int64_t ldd, int64_t rows, int64_t dim, int dtype, void* stream);
 
 /* out[i] = a[i] + b[i] (fp32 arithmetic, one rounding): sums the latent gradients of a view that takes part in several
- * multiview pairs (x_clip.py:750-755,851-868) */
+ * multiview pairs (x_clip.py:750-755,851-868).  `count` need not be a multiple of the 16-byte chunk (a scalar tail). */
 int xclip_add(const void* a, const void* b, void* out, int64_t count, int dtype, void* stream);
 
 /* table_accum[idx[r], :] += src[r, :] (fp32; NULL: skipped) and colsum_accum[:] += sum_r src[r, :] (fp32; NULL: skipped):
@@ -145,7 +145,13 @@ int64_t xclip_gemm_small_limit(int64_t max_flop);
 /* ---- the inference returns (reference CLIP.forward with return_loss = False, x_clip.py:740-746) --------------------------------
  * xclip_gemm_batched: `batch` independent products C_z[M,N] = alpha * op(A_z) op(B_z) with xclip_gemm's operand layouts, problem z at
  *   A + z*stride_a (elements) etc.: einsum('b t d, b i d -> b t i') of the fine-grained (FILIP) similarities (0, 0) and its two gradients
- *   (0, 1) / (1, 1).  No optional terms.
+ *   (0, 1) / (1, 1).  No optional terms.  N, the leading dimensions and the batch strides are multiples of the 16-byte chunk; M and K
+ *   need not be.  Padding (tests/kernel_cases.py case_bmm holds both halves):
+ *     a NORMAL operand (A[m*lda + k], B[n*ldb + k]) is read in whole chunks along k, the one that straddles K included: its elements
+ *       [K, K rounded up to the chunk) of every row must be ZERO (lda / ldb cover the rounded K); nothing behind them is read;
+ *     a K-MAJOR operand (A[k*lda + m], B[k*ldb + n]) is masked by contraction row: rows >= K -- the next problem of the batch, or
+ *       whatever follows the last one -- are never read.  Its columns [M, M rounded up) (lda covers the rounded M) are read but reach
+ *       only output rows >= M, which are never stored: they may hold anything; nothing behind them is read.
  * xclip_rowdot: out[r] = <a[r,:], b[r,:]> in the operands' dtype: einsum('b d, b d -> b') of the matched pairs. */
 int xclip_gemm_batched(int a_kmajor, int b_kmajor, const void* A, int64_t lda, int64_t stride_a, const void* B, int64_t ldb, int64_t stride_b,
                        void* C, int64_t ldc, int64_t stride_c, int64_t batch, int64_t M, int64_t N, int64_t K, float alpha, int dtype,
@@ -295,13 +301,15 @@ int xclip_sigloss_grad(const void* Q, const void* K, int64_t nq, int64_t nk, int
  * temperature), row stride lds.  reduce: t2i[x, y0+y] = sum_t w[x,t] max_k temp*s / max(sum_t w, 1e-6), i2t[x, y0+y] = mean_k
  * max_{t: w[x,t]} temp*s (both [bx, ldo] fp32), plus the arg-max positions kmax [bx, nt, ytotal], tmax [bx, ytotal, ni] (int16).
  * route: the chunk of d loss / d s, P[(x,t),(y,k)] = temp (g1[x,y0+y] w[x,t] / cnt[x] [k == kmax] + g2[x,y0+y] / ni [t == tmax]),
- * in `dtype`, row stride ldp (padding columns zero); the backward then is dT += P I and dI = P^T T through xclip_gemm.
+ * in `dtype`, row stride ldp; columns [yc ni, pcols) are written as zeros (pcols a multiple of the 16-byte chunk, yc ni <= pcols <= ldp:
+ * the padding the GEMMs behind it contract over) and columns [pcols, ldp) are left alone, so P may be a column view of a wider buffer;
+ * the backward then is dT += P I and dI = P^T T through xclip_gemm.
  * mask: [bx, nt] bytes (text != pad_id, x_clip.py:614); cnt [bx] fp32 = number of real tokens per text (written by reduce when
  * its chunk holds global column 0); log_temp: device fp32 scalar (the temperature parameter). */
 int xclip_filip_reduce(const void* S, int64_t lds, const uint8_t* mask, const float* log_temp, float* t2i, float* i2t, int64_t ldo,
                        int16_t* kmax, int16_t* tmax, float* cnt, int64_t bx, int64_t nt, int64_t yc, int64_t ni, int64_t y0,
                        int64_t ytotal, int dtype, void* stream);
-int xclip_filip_route(void* P, int64_t ldp, const uint8_t* mask, const float* log_temp, const float* g1, const float* g2, int64_t ldg,
+int xclip_filip_route(void* P, int64_t ldp, int64_t pcols, const uint8_t* mask, const float* log_temp, const float* g1, const float* g2, int64_t ldg,
                       const int16_t* kmax, const int16_t* tmax, const float* cnt, int64_t bx, int64_t nt, int64_t yc, int64_t ni,
                       int64_t y0, int64_t ytotal, int dtype, void* stream);
 /* The same forward with the reductions INSIDE the token-similarity GEMM (x_clip.py:797-811 fused: the 'x t d, y i d -> x y t i' block is

@@ -1194,3 +1194,333 @@ def case_dropout(dev, dtype, n=4096 + 8 * 37, p=0.3, seed=0x1234567890ABCDEF):
     ops.dropout(z, p, seed, out=z)
     assert torch.equal(z, y)
     assert torch.equal(ops.dropout(x.to(dev), 0.0, seed), x.to(dev))
+
+
+# ---- the chunked FILIP head (filip.h) and the inference-return products (gemm.h batched, rows.h rowdot), kernel by kernel -----------------
+def _roundup(n, m):
+    return (n + m - 1) // m * m
+
+
+def filip_mask(bx, nt, seed=63):
+    """text 0 full; ragged lengths for the rest; text 1 a single token; text 2 (if there is one) with a hole at position 1"""
+    g = torch.Generator().manual_seed(seed)
+    mask = torch.ones(bx, nt, dtype=torch.bool)
+    for x in range(1, bx):
+        mask[x, int(torch.randint(min(3, nt), nt + 1, (1,), generator=g)):] = False
+    if bx > 2:
+        mask[2, 1] = False
+    if bx > 1:
+        mask[1, 1:] = False
+    return mask
+
+
+def filip_route_ref(mask, g1, g2, kmax, tmax, cnt, temp, ni, yc, y0, width):
+    """include/xclip.h: P[(x,t),(y,k)] = temp (g1[x,y0+y] w[x,t] / cnt[x] [k == kmax[x,t,y0+y]] + g2[x,y0+y] / ni [t == tmax[x,y0+y,k]]) in fp64,
+    zero in the padding columns [yc ni, width) -> (P [bx nt, width], how many elements carry BOTH families)"""
+    bx, nt = mask.shape
+    w = mask.double()
+    ys = slice(y0, y0 + yc)
+    assert bool(mask.gather(1, tmax.long().reshape(bx, -1)).all()), "tmax names a padding token: not a map xclip_filip_reduce can produce"
+    hit1 = kmax[:, :, ys].long()[..., None] == torch.arange(ni)                          # [bx, nt, yc, ni]
+    hit2 = tmax[:, ys].long()[:, None] == torch.arange(nt)[None, :, None, None]          # [bx, nt, yc, ni]
+    a1 = g1[:, ys].double()[:, None, :, None] * (w / cnt.double()[:, None])[:, :, None, None]
+    a2 = g2[:, ys].double()[:, None, :, None] / ni
+    P = temp * (a1 * hit1 + a2 * hit2)
+    out = torch.zeros(bx * nt, width, dtype=torch.float64)
+    out[:, : yc * ni] = P.reshape(bx * nt, yc * ni)
+    return out, int((hit1 & hit2 & mask[:, :, None, None]).sum())
+
+
+def filip_route_check(dev, dtype, mask, g1, g2, maps_dev, maps_ref, ni, yc, y0, ldp_extra, name):
+    """one xclip_filip_route call on the maps `maps_dev` = (kmax, tmax, cnt) against the header's formula evaluated on `maps_ref`: exact zeros
+    wherever the formula is zero (padding rows, padding columns up to the width of P, unselected elements), one rounding elsewhere, and nothing
+    written outside P -- P is a view [:bx nt, :ldp] of a NaN-filled [bx nt + 2, ldp + 16] buffer"""
+    bx, nt = mask.shape
+    v = ops.vec(dtype)
+    ldp = _roundup(yc * ni, v) + ldp_extra
+    tau = torch.tensor([0.37], dtype=torch.float32)
+    full = torch.full((bx * nt + 2, ldp + 16), float("nan"), dtype=dtype, device=dev)
+    P = full[: bx * nt, :ldp]
+    ops.filip_route(P, mask.to(torch.uint8).to(dev), tau.to(dev), g1.to(dev), g2.to(dev), *maps_dev, nt, ni, yc, y0)
+    ref, both = filip_route_ref(mask, g1, g2, *maps_ref, math.exp(float(tau)), ni, yc, y0, ldp)
+    assert both > 0, "no element where the two families add"
+    got = full.cpu()
+    assert bool(torch.isnan(got[bx * nt:].float()).all()), f"{name}: the rows behind P were written"
+    assert bool(torch.isnan(got[:, ldp:].float()).all()), f"{name}: the columns behind P's width were written"
+    got = got[: bx * nt, :ldp].double()
+    zero = ref == 0
+    assert bool((got[zero] == 0).all()), f"{name}: {int((got[zero] != 0).sum())} elements that must be exactly zero are not (first: {(zero & (got != 0)).nonzero()[:4].tolist()})"
+    assert int((~zero).sum()) > 0
+    close(got, ref, dtype, name)
+    return both
+
+
+def case_filip_route(dev, dtype, bx, nt, ni, yc, y0, ytotal, ldp_extra):
+    """filip.h filip_route_kernel on inputs made directly (no forward pass): kmax random in [0, ni) -- also in the rows of padding tokens, which
+    the row-coalesced reduction never writes and the route kernel must not use; tmax random among the REAL tokens of its text (a subset of
+    [0, nt): the header's second family carries no w[x, t] because xclip_filip_reduce takes tmax over real tokens only); elements where both
+    families hit are planted at the first and last column, on both sides of the first slice boundary, and in every text"""
+    v = ops.vec(dtype)
+    g = torch.Generator().manual_seed(6100 + ni * 7 + yc + y0)
+    mask = filip_mask(bx, nt)
+    cnt = mask.sum(-1).float()
+    kmax = torch.randint(0, ni, (bx, nt, ytotal), generator=g).to(torch.int16)
+    tmax = torch.empty(bx, ytotal, ni, dtype=torch.int16)
+    ncols = yc * ni
+    plant = sorted({0, ncols - 1, ncols // 2} | ({256 * v - 1, 256 * v} if 256 * v < ncols else set()))
+    for x in range(bx):
+        real = mask[x].nonzero().flatten()
+        tmax[x] = real[torch.randint(0, real.numel(), (ytotal, ni), generator=g)].to(torch.int16)
+        for j, c in enumerate(plant):
+            t, y, k = int(real[(real.numel() - 1 - j) % real.numel()]), c // ni, c % ni
+            kmax[x, t, y0 + y] = k
+            tmax[x, y0 + y, k] = t
+    g1 = torch.randn(bx, ytotal, generator=g)
+    g2 = torch.randn(bx, ytotal, generator=g)
+    maps = (kmax, tmax, cnt)
+    return filip_route_check(dev, dtype, mask, g1, g2, tuple(m.to(dev) for m in maps), maps, ni, yc, y0, ldp_extra, "filip route P")
+
+
+def case_filip_reduce(dev, dtype, bx, nt, ni, by, chunks, lds_extra, chain=False):
+    """filip.h filip_reduce_rows_kernel (ni >= the 16-byte chunk) / filip_reduce_kernel (below it) on a similarity matrix made directly, ties
+    everywhere: values on the bf16 grid in both storage types (distinct values stay distinct and equal ones equal under the multiplication by
+    temp), every other row quantised to 33 levels, one constant row, one constant column.  One call per chunk of ceil(by / chunks) images,
+    each from a buffer of its own whose columns behind the chunk hold +1e30.  The arg-max maps are compared EXACTLY with numpy's
+    first-occurrence arg-max of the fp64 matrix.  chain: the kernel's own maps then go through xclip_filip_route, against the header's formula
+    on the REFERENCE maps"""
+    v = ops.vec(dtype)
+    g = torch.Generator().manual_seed(6200 + ni * 5 + by)
+    mask = filip_mask(bx, nt)
+    S = torch.randn(bx * nt, by * ni, generator=g).to(torch.bfloat16).float()
+    S[::2] = (S[::2] * 4).round().clamp(-16, 16) / 4
+    S[:, ni + min(3, ni - 1)] = 6.0                                  # a constant column at the top: every token ties in it
+    S[nt + 0] = 6.0                                                  # a constant row (text 1's only real token): every k ties, in every image
+    S[2] = -6.0                                                      # and one of text 0's at the bottom
+    S = S.to(dtype)
+    tau = torch.tensor([0.37], dtype=torch.float32)
+    temp = math.exp(float(tau))
+    nan = float("nan")
+    t2i = torch.full((bx, by), nan, dtype=torch.float32, device=dev)
+    i2t = torch.full((bx, by), nan, dtype=torch.float32, device=dev)
+    kmax = torch.full((bx, nt, by), -1, dtype=torch.int16, device=dev)
+    tmax = torch.full((bx, by, ni), -1, dtype=torch.int16, device=dev)
+    cnt = torch.full((bx,), -1.0, dtype=torch.float32, device=dev)
+    m8 = mask.to(torch.uint8).to(dev)
+    yc = (by + chunks - 1) // chunks
+    for y0 in range(0, by, yc):
+        ycc = min(yc, by - y0)
+        buf = torch.full((bx * nt, _roundup(ycc * ni, v) + lds_extra), 1e30, dtype=dtype)
+        buf[:, : ycc * ni] = S[:, y0 * ni: (y0 + ycc) * ni]
+        ops.filip_reduce(buf.to(dev), m8, tau.to(dev), t2i, i2t, kmax, tmax, cnt, nt, ni, ycc, y0)
+    S4 = ref64(S).view(bx, nt, by, ni)
+    kmax_r = torch.from_numpy(np.argmax(S4.numpy(), axis=3))                            # [bx, nt, by], first occurrence
+    Sm = S4.masked_fill(~mask[:, :, None, None], -float("inf"))
+    tmax_r = torch.from_numpy(np.argmax(Sm.numpy(), axis=1))                            # [bx, by, ni], first occurrence among the real tokens
+    w = mask.double()
+    t2i_r = (temp * S4.amax(3) * w[:, :, None]).sum(1) / w.sum(1).clamp_min(1e-6)[:, None]
+    i2t_r = (temp * Sm.amax(1)).mean(-1)
+    km, tm = kmax.cpu().long(), tmax.cpu().long()
+    live = mask[:, :, None].expand_as(km)
+    assert int((km[live] == -1).sum()) == 0 and int((tm == -1).sum()) == 0, "an arg-max entry was never written"
+    assert torch.equal(km[live], kmax_r[live]), f"kmax differs from the first-occurrence arg-max at {int((km != kmax_r)[live].sum())} real (token, image) pairs"
+    assert bool(mask.gather(1, tm.clamp(0, nt - 1).reshape(bx, -1)).all()), "tmax names a padding token"
+    assert torch.equal(tm, tmax_r), f"tmax differs from the first-occurrence arg-max over the real tokens at {int((tm != tmax_r).sum())} columns"
+    assert torch.equal(cnt.cpu(), mask.sum(-1).float())
+    close(t2i, t2i_r, torch.float32, "filip reduce t2i" + (" <- bf16" if dtype == torch.bfloat16 else ""))
+    close(i2t, i2t_r, torch.float32, "filip reduce i2t" + (" <- bf16" if dtype == torch.bfloat16 else ""))
+    if chain:
+        g1 = torch.randn(bx, by, generator=g)
+        g2 = torch.randn(bx, by, generator=g)
+        kmax_ref = kmax_r.to(torch.int16)
+        for y0 in range(0, by, yc):
+            filip_route_check(dev, dtype, mask, g1, g2, (kmax, tmax, cnt), (kmax_ref, tmax_r.to(torch.int16), mask.sum(-1).float()), ni,
+                              min(yc, by - y0), y0, 0, "filip reduce -> route P")
+
+
+def case_rowlse_rowgrad(dev, rows, cols, diag_off, dcl, lds_extra, spread):
+    """filip.h rowlse_kernel / rowgrad_kernel against the two lines of include/xclip.h in fp64, rows whose diagonal column r + diag_off lies
+    outside [0, cols) included (no positive term, nothing left out).  S is a view of a buffer whose extra columns hold +1e30, G a view of a
+    NaN-filled buffer four columns wider; both accumulators start non-zero (the contract is +=).  A row that sums nothing (cols = 1, dcl,
+    row 0) has lse = log(1e-20) (filip.h: `l > 0 ? m + logf(l) : logf(1e-20f)`; the header's sum is empty there) and G = -gmul coef at its
+    diagonal.  rowgrad is given the lse rowlse produced -- its input -- and the reference G is formed from those same fp32 values; fast_exp
+    (__expf: exp2 of x log2(e), an argument error of 2^-24 |x| log2(e)) stays below 1e-7 of the largest element for any x > -88, so the wide
+    spread needs no wider bar.  loss / dtau increments: sums through float atomics in arbitrary order, held to the fp32 bar of the sum of
+    the absolute values of their terms"""
+    g = torch.Generator().manual_seed(6300 + rows + cols)
+    Sb = torch.full((rows, cols + lds_extra), 1e30, dtype=torch.float32)
+    Sb[:, :cols] = torch.randn(rows, cols, generator=g) * spread
+    coef, gmul, loss0, dtau0 = 0.5 / rows, 0.7, 0.5, -0.25
+    loss = torch.full((1,), loss0, dtype=torch.float32, device=dev)
+    dtau = torch.full((1,), dtau0, dtype=torch.float32, device=dev)
+    Sd = Sb.to(dev)[:, :cols]
+    lse = ops.rowlse(Sd, diag_off, dcl, coef, loss)
+    Gb = torch.full((rows, cols + 4), float("nan"), dtype=torch.float32, device=dev)
+    G = ops.rowgrad(Sd, lse, diag_off, dcl, coef, torch.tensor([gmul], dtype=torch.float32).to(dev), dtau, out=Gb[:, :cols])
+    assert bool(torch.isnan(Gb[:, cols:]).all()), "rowgrad wrote behind its columns"
+    S = ref64(Sb[:, :cols])
+    r = torch.arange(rows)
+    valid = (r + diag_off >= 0) & (r + diag_off < cols)
+    diag = torch.zeros(rows, cols, dtype=torch.bool)
+    diag[r[valid], (r + diag_off)[valid]] = True
+    lse_r = torch.logsumexp(S.masked_fill(diag, -float("inf")) if dcl else S, 1)
+    empty = torch.isinf(lse_r)
+    assert int(empty.sum()) == (1 if (dcl and cols == 1 and diag_off == 0) else 0)
+    lse_r[empty] = math.log(1e-20)
+    tag = f" (spread {spread})"
+    close(lse, lse_r, torch.float32, "rowlse lse" + tag)
+    pos = torch.zeros(rows, dtype=torch.float64)
+    pos[valid] = S[diag]
+    terms = coef * (lse_r - pos)
+    got = loss.cpu().double() - loss0
+    assert float(got.abs()) > 0 or float(terms.abs().sum()) == 0
+    close(got, terms.sum().reshape(1), torch.float32, "rowlse loss increment" + tag, scale=float(terms.abs().sum()))
+    lq = lse.cpu().double()
+    Gr = gmul * coef * ((S - lq[:, None]).exp() * ((~diag).double() if dcl else 1.0) - diag.double())
+    close(G, Gr, torch.float32, "rowgrad G" + tag, scale=abs(gmul * coef))
+    got = dtau.cpu().double() - dtau0
+    close(got, (Gr * S).sum().reshape(1), torch.float32, "rowgrad dtau increment" + tag, scale=float((Gr * S).abs().sum()))
+    assert float(loss.cpu()) != float(terms.sum().float()) and float(dtau.cpu()) != float((Gr * S).sum().float()), "an accumulator was overwritten, not added to"
+
+
+def _strided_operand(dtype, B, rows, cols, ld, gap, seed, zero_to=None):
+    """a [B, rows, cols] view (row stride ld, problem stride rows ld + gap) into a NaN-filled buffer with NaN in front of problem 0, behind
+    problem B - 1, between the problems and between a row's `cols` elements and ld -- except columns [cols, zero_to), which hold zeros"""
+    v = ops.vec(dtype)
+    stride, front = rows * ld + gap, 2 * v
+    buf = torch.full((front + B * stride + 2 * v,), float("nan"), dtype=dtype)
+    view = torch.as_strided(buf, (B, rows, cols), (stride, ld, 1), front)
+    view.copy_(rnd((B, rows, cols), dtype, seed))
+    if zero_to is not None and zero_to > cols:
+        torch.as_strided(buf, (B, rows, zero_to - cols), (stride, ld, 1), front + cols).zero_()
+    return buf, (lambda b: torch.as_strided(b, (B, rows, cols), (stride, ld, 1), front))
+
+
+def case_bmm(dev, dtype, B, M, N, K, layout, alpha=1.0):
+    """gemm.h gemm_kernel over blockIdx.z (xclip_gemm_batched) against a per-problem fp64 product.  Asymmetric operands, each a view into a
+    NaN-filled buffer.  The pad contract of include/xclip.h, both halves: a NORMAL operand's columns [K, K rounded up to the chunk) hold zeros
+    (load_normal reads the straddling chunk whole), NaN behind them up to the leading dimension; a K-MAJOR operand has NaN in everything
+    behind its row K - 1 (the gap to the next problem: load_kmajor masks by contraction row) and behind its M (or N) columns up to the
+    leading dimension (columns [M, M rounded up) are read, and reach only output rows that are never stored)"""
+    v = ops.vec(dtype)
+    a_k, b_k = layout == "tn", layout in ("nn", "tn")
+    Kp = _roundup(K, v)
+    if a_k:
+        abuf, aview = _strided_operand(dtype, B, K, M, _roundup(M, v) + v, 2 * (_roundup(M, v) + v), 171)
+    else:
+        abuf, aview = _strided_operand(dtype, B, M, K, Kp + v, 2 * v, 171, zero_to=Kp)
+    if b_k:
+        bbuf, bview = _strided_operand(dtype, B, K, N, N + v, 2 * (N + v), 172)
+    else:
+        bbuf, bview = _strided_operand(dtype, B, N, K, Kp + v, 2 * v, 172, zero_to=Kp)
+    c = ops.bmm(aview(abuf.to(dev)), bview(bbuf.to(dev)), M, N, K, a_k, b_k, alpha)
+    A, Bm = ref64(aview(abuf)), ref64(bview(bbuf))
+    r = alpha * ((A.transpose(1, 2) if a_k else A) @ (Bm if b_k else Bm.transpose(1, 2)))
+    assert tuple(c.shape) == (B, M, N)
+    close(c, r, dtype, f"bmm {layout}" + ("" if alpha == 1.0 else f" alpha {alpha}"))
+
+
+def case_bmm_rejects_tt(dev, dtype):
+    """(A k-major, B normal) is the one layout xclip_gemm_batched does not carry: an error, not a wrong product"""
+    import pytest
+    a, b = rnd((2, 16, 8), dtype, 173).to(dev), rnd((2, 8, 16), dtype, 174).to(dev)
+    with pytest.raises(RuntimeError, match="xclip_gemm_batched"):
+        ops.bmm(a, b, 8, 8, 16, True, False)
+
+
+def case_bmm_many(dev, B=65536 + 2, M=8, N=8, K=8):
+    """more problems than one launch carries (ops.bmm splits at 65535): every problem against fp64"""
+    a, b = rnd((B, M, K), torch.float32, 175), rnd((B, N, K), torch.float32, 176)
+    c = ops.bmm(a.to(dev), b.to(dev), M, N, K)
+    close(c, ref64(a) @ ref64(b).transpose(1, 2), torch.float32, "bmm nt across the launch split")
+
+
+def case_rowdot(dev, dtype, rows):
+    """rows.h rowdot_kernel at every chunks-per-lane dispatch (bf16 rows of 8 .. 4096 elements: 1, 1, 1, 2, 4, 8 chunks per lane; fp32 rows of
+    4 .. 4096: 1, 1, 1, 2, 4, 8, 16), contiguous and as row-strided views into NaN-filled buffers (ops.rowdot reads such views in place),
+    against the fp64 dot product; each element to one rounding of a sum whose terms add up to max_r sum |a b|"""
+    v = ops.vec(dtype)
+    dims = (8, 24, 512, 1024, 2048, 4096) if dtype == torch.bfloat16 else (4, 12, 256, 512, 1024, 2048, 4096)
+    for dim in dims:
+        a, b = rnd((rows, dim), dtype, 181), rnd((rows, dim), dtype, 182)
+        want = (ref64(a) * ref64(b)).sum(-1)
+        scale = float((ref64(a) * ref64(b)).abs().sum(-1).max())
+        close(ops.rowdot(a.to(dev), b.to(dev)), want, dtype, "rowdot", scale=scale)
+        ab = torch.full((rows, dim + v), float("nan"), dtype=dtype)
+        bb = torch.full((rows, dim + 3 * v), float("nan"), dtype=dtype)
+        ab[:, :dim], bb[:, :dim] = a, b
+        close(ops.rowdot(ab.to(dev)[:, :dim], bb.to(dev)[:, :dim]), want, dtype, "rowdot strided", scale=scale)
+
+
+def _cast_inputs():
+    """fp32 bit patterns around every rounding decision of the bf16 conversion"""
+    bits = [0x00000000, 0x80000000,
+            0x3F808000, 0x3F808001, 0x3F807FFF,                      # halfway above an EVEN bf16 (ties to it), just above, just below
+            0x3F818000, 0x3F818001, 0x3F817FFF,                      # halfway above an ODD bf16 (ties away from it), just above, just below
+            0xBF808000, 0xBF808001, 0xBF807FFF, 0xBF818000, 0xBF818001, 0xBF817FFF,
+            0x7F7F0000, 0x7F7F7FFF, 0x7F7F8000, 0x7F7FFFFF,          # the largest finite bf16, just below its halfway point, the halfway point, FLT_MAX
+            0xFF7F0000, 0xFF7F7FFF, 0xFF7F8000, 0xFF7FFFFF,
+            0x7F800000, 0xFF800000, 0x7FC00000]                      # +-inf, NaN
+    return torch.from_numpy(np.array(bits, dtype=np.uint32).view(np.float32).copy())
+
+
+def case_cast_and_add(dev, dtype):
+    """tokens.h cast_from_f32_kernel and add_rows_kernel, bit for bit against the CPU's fp32 arithmetic and round-to-nearest-even conversion, at
+    counts that are no multiple of anything (1, 7, 4096 + 37)"""
+    ints = torch.int16 if dtype == torch.bfloat16 else torch.int32
+    special = _cast_inputs()
+    for count in (1, 7, 4096 + 37):
+        for scale in (1.0, 0.125, 1.0 / 3.0):
+            src = torch.cat([special, rnd((4096 + 37,), torch.float32, 191, 3.0)])
+            src = src[2:3] if count == 1 else (src[2: 2 + count] if count == 7 else src[:count])
+            if count > 7:
+                assert bool(torch.isnan(src).any()) and bool(torch.isinf(src).any())
+            got = ops.cast_from_f32(src.to(dev).contiguous(), dtype, scale).cpu()
+            want = (src * torch.tensor(scale, dtype=torch.float32)).to(dtype)
+            nan = torch.isnan(want.float())
+            assert torch.equal(torch.isnan(got.float()), nan), "NaN must map to NaN, and nothing else may"
+            assert torch.equal(got.view(ints)[~nan], want.view(ints)[~nan]), (count, scale, int((got.view(ints) != want.view(ints))[~nan].sum()))
+        a, b = rnd((count,), dtype, 192, 3.0), rnd((count,), dtype, 193, 3.0)
+        got = ops.add_rows(a.to(dev), b.to(dev)).cpu()
+        assert torch.equal(got.view(ints), (a.float() + b.float()).to(dtype).view(ints)), count
+
+
+# The parameter sets of the cases above, shared by the emulator and the GPU suite (the shapes are the smallest that reach each branch;
+# nothing here gets larger on the GPU).  Each id names the branch its set exists for.
+BF, FP = torch.bfloat16, torch.float32
+FILIP_ROUTE_SETS = {   # id: (dtype, bx, nt, ni, yc, y0, ytotal, ldp_extra)
+    "bf16-2450cols-two-slices-boundary-inside-an-image-odd-ni-both-tbase-parities": (BF, 3, 12, 49, 50, 0, 50, 0),
+    "bf16-chunk-in-mid-batch-y0-3-tbase-parity-moves-with-x-and-y0": (BF, 3, 12, 49, 50, 3, 57, 0),
+    "bf16-last-partial-chunk-in-the-full-row-stride-trailing-padding-and-a-padding-only-slice": (BF, 3, 12, 49, 7, 50, 57, 2456 - 344),
+    "bf16-even-ni-64-wide-tmax-load-always-chunks-never-straddle-images": (BF, 3, 9, 64, 40, 0, 40, 0),
+    "bf16-ni-3-chunk-spans-3-to-4-images-683-images-kmax-staged-in-batches-of-23-rows": (BF, 2, 50, 3, 700, 0, 700, 0),
+    "bf16-third-slice-padding-only-live_slice-false": (BF, 3, 12, 49, 50, 0, 50, 4104 - 2456),
+    "fp32-vec-4-1024-column-slices-1170cols-two-slices": (FP, 2, 7, 9, 130, 0, 130, 0),
+    "fp32-ni-98-five-images-y0-2": (FP, 3, 12, 98, 5, 2, 9, 0),
+}
+FILIP_REDUCE_SETS = {  # id: (dtype, bx, nt, ni, by, chunks, lds_extra, chain)
+    "bf16-rows-kernel-ni-49-one-chunk-image-split-over-blockIdx.y-then-route": (BF, 3, 12, 49, 12, 1, 0, True),
+    "bf16-rows-kernel-ni-49-three-chunks-y0-above-0-chunks-straddle-segments-then-route": (BF, 3, 12, 49, 12, 3, 0, True),
+    "bf16-rows-kernel-ni-64-aligned-segments": (BF, 3, 12, 64, 9, 1, 0, False),
+    "bf16-rows-kernel-ni-9-chunk-columns-no-whole-number-of-16-byte-chunks": (BF, 3, 12, 9, 5, 2, 0, False),
+    "bf16-per-pair-kernel-ni-5-below-the-chunk": (BF, 3, 12, 5, 6, 2, 0, False),
+    "fp32-rows-kernel-ni-49-vec-4": (FP, 3, 12, 49, 6, 1, 0, False),
+    "fp32-per-pair-kernel-ni-3": (FP, 3, 12, 3, 4, 2, 0, False),
+    "bf16-rows-kernel-ni-49-row-stride-8-columns-wider-than-the-chunk": (BF, 3, 12, 49, 12, 3, 8, False),
+}
+ROWLSE_SETS = {        # id: (rows, cols, diag_off, lds_extra)
+    "5x70": (5, 70, 0, 3),
+    "7x63-diag-off-2": (7, 63, 2, 0),
+    "6x65-diag-off-minus-3-rows-0-to-2-have-no-diagonal": (6, 65, -3, 1),
+    "4x1-one-column-dcl-row-0-sums-nothing": (4, 1, 0, 2),
+    "3x200-diag-off-190-diagonal-falls-off-the-right-edge": (3, 200, 190, 0),
+    "1500x1500-rowgrad-capped-at-8192-work-groups-grid-stride-loop": (1500, 1500, 0, 4),
+}
+BMM_SETS = {           # id: (layout, M, N, K, alpha)
+    "nt-77x104x512-several-k-steps": ("nt", 77, 104, 512, 1.0),
+    "nt-257x200x64-three-m-tiles-two-n-tiles": ("nt", 257, 200, 64, 1.0),
+    "nn-77x512x98-k-tail-four-n-tiles": ("nn", 77, 512, 98, 1.0),
+    "nn-9x64x49-k-below-one-step": ("nn", 9, 64, 49, 1.0),
+    "tn-98x512x77-ragged-m-and-k-lda-m-rounded-up": ("tn", 98, 512, 77, 1.0),
+    "tn-49x64x9": ("tn", 49, 64, 9, 1.0),
+    "nn-77x512x98-alpha-0.5": ("nn", 77, 512, 98, 0.5),
+}

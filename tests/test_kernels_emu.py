@@ -701,3 +701,51 @@ def test_attention_pool(dtype, batch, n, heads, masked, hd, row, causal):
     """attention for one query row per (sample, head): key counts that are not multiples of the keys per wave-load (8 / 4 / 16), masks with a
     hole and a padded tail, both head-slot widths, a pooled row in the middle under a causal mask"""
     K.case_attention_pool(DEV, dtype, batch, n, heads, masked, hd, row, causal)
+
+
+# ---- the chunked FILIP head and the inference-return products, kernel by kernel (tests/kernel_cases.py: one id per branch) ---------------
+@pytest.mark.parametrize("name", list(K.FILIP_ROUTE_SETS))
+def test_filip_route(name):
+    dtype, *shape = K.FILIP_ROUTE_SETS[name]
+    K.case_filip_route(DEV, dtype, *shape)
+
+
+@pytest.mark.parametrize("name", list(K.FILIP_REDUCE_SETS))
+def test_filip_reduce(name):
+    dtype, *shape, chain = K.FILIP_REDUCE_SETS[name]
+    K.case_filip_reduce(DEV, dtype, *shape, chain=chain)
+
+
+@pytest.mark.parametrize("spread", [1, 60])
+@pytest.mark.parametrize("dcl", [False, True], ids=["infonce", "dcl"])
+@pytest.mark.parametrize("name", list(K.ROWLSE_SETS))
+def test_rowlse_rowgrad(name, dcl, spread):
+    rows, cols, diag_off, lds_extra = K.ROWLSE_SETS[name]
+    K.case_rowlse_rowgrad(DEV, rows, cols, diag_off, dcl, lds_extra, spread)
+
+
+@pytest.mark.parametrize("dtype", K.DTYPES, ids=["fp32", "bf16"])
+@pytest.mark.parametrize("name", list(K.BMM_SETS))
+def test_bmm(name, dtype):
+    layout, M, N, K_, alpha = K.BMM_SETS[name]
+    K.case_bmm(DEV, dtype, 3, M, N, K_, layout, alpha)
+
+
+@pytest.mark.parametrize("dtype", K.DTYPES, ids=["fp32", "bf16"])
+def test_bmm_rejects_a_kmajor_b_normal(dtype):
+    K.case_bmm_rejects_tt(DEV, dtype)
+
+
+def test_bmm_across_the_launch_split():
+    K.case_bmm_many(DEV)
+
+
+@pytest.mark.parametrize("dtype", K.DTYPES, ids=["fp32", "bf16"])
+@pytest.mark.parametrize("rows", [1, 5, 1027])
+def test_rowdot(dtype, rows):
+    K.case_rowdot(DEV, dtype, rows)
+
+
+@pytest.mark.parametrize("dtype", K.DTYPES, ids=["fp32", "bf16"])
+def test_cast_and_add(dtype):
+    K.case_cast_and_add(DEV, dtype)

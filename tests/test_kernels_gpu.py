@@ -490,3 +490,51 @@ def test_attention_dropout(dtype, n, heads, masked, causal, hd):
 def test_dropout(dtype):
     K.case_dropout(DEV, dtype)
     K.case_dropout(DEV, dtype, n=(1 << 25) + 4096, p=0.1)              # many work-groups, grid-stride loop
+
+
+# ---- the chunked FILIP head and the inference-return products, kernel by kernel (tests/kernel_cases.py: one id per branch) ---------------
+@pytest.mark.parametrize("name", list(K.FILIP_ROUTE_SETS))
+def test_filip_route(name):
+    dtype, *shape = K.FILIP_ROUTE_SETS[name]
+    K.case_filip_route(DEV, dtype, *shape)
+
+
+@pytest.mark.parametrize("name", list(K.FILIP_REDUCE_SETS))
+def test_filip_reduce(name):
+    dtype, *shape, chain = K.FILIP_REDUCE_SETS[name]
+    K.case_filip_reduce(DEV, dtype, *shape, chain=chain)
+
+
+@pytest.mark.parametrize("spread", [1, 60])
+@pytest.mark.parametrize("dcl", [False, True], ids=["infonce", "dcl"])
+@pytest.mark.parametrize("name", list(K.ROWLSE_SETS))
+def test_rowlse_rowgrad(name, dcl, spread):
+    rows, cols, diag_off, lds_extra = K.ROWLSE_SETS[name]
+    K.case_rowlse_rowgrad(DEV, rows, cols, diag_off, dcl, lds_extra, spread)
+
+
+@pytest.mark.parametrize("dtype", K.DTYPES, ids=IDS)
+@pytest.mark.parametrize("name", list(K.BMM_SETS))
+def test_bmm(name, dtype):
+    layout, M, N, K_, alpha = K.BMM_SETS[name]
+    K.case_bmm(DEV, dtype, 3, M, N, K_, layout, alpha)
+
+
+@pytest.mark.parametrize("dtype", K.DTYPES, ids=IDS)
+def test_bmm_rejects_a_kmajor_b_normal(dtype):
+    K.case_bmm_rejects_tt(DEV, dtype)
+
+
+def test_bmm_across_the_launch_split():
+    K.case_bmm_many(DEV)
+
+
+@pytest.mark.parametrize("dtype", K.DTYPES, ids=IDS)
+@pytest.mark.parametrize("rows", [1, 5, 1027])
+def test_rowdot(dtype, rows):
+    K.case_rowdot(DEV, dtype, rows)
+
+
+@pytest.mark.parametrize("dtype", K.DTYPES, ids=IDS)
+def test_cast_and_add(dtype):
+    K.case_cast_and_add(DEV, dtype)

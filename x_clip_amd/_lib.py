@@ -65,7 +65,7 @@ _SIGNATURES = {
     "xclip_filip_fused_ok": (c_int, [L, L, L, I]),
     "xclip_filip_fused_workspace_bytes": (c_int64, [L, L, L, L]),
     "xclip_filip_fused_fwd": (c_int, [P, P, P, P, P, P, L, P, P, P, P, L, L, L, L, L, L, L, L, I, P]),
-    "xclip_filip_route": (c_int, [P, L, P, P, P, P, L, P, P, P, L, L, L, L, L, L, I, P]),
+    "xclip_filip_route": (c_int, [P, L, L, P, P, P, P, L, P, P, P, L, L, L, L, L, L, I, P]),
     "xclip_rowlse": (c_int, [P, L, L, L, L, I, F, P, P, P]),
     "xclip_rowgrad": (c_int, [P, L, P, L, L, L, I, F, P, P, L, P, P]),
     "xclip_simreg_diff": (c_int, [P, L, P, L, P, L, L, L, L, P, I, P]),
@@ -102,7 +102,7 @@ _SIGNATURES = {
     "xclip_adamw_step": (c_int, [P, L, L, I, I, P, P, P, P, P, D, D, D, D, D, P]),
 }
 EXPORTS = tuple(_SIGNATURES)
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 
 def _bind(path: str):

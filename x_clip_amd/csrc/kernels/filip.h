@@ -233,13 +233,14 @@ __global__ __launch_bounds__(256) void filip_reduce_rows_kernel(const T* __restr
 // History (configs[3], 1 GB chunk; profiles/r03_d / r03_h / r03_i_kernel_stats_filip.txt): a flat (row, chunk) index with two 64-bit
 // divisions and ~14 narrow global loads per 16 bytes written: 0.64 ms = 1.5 TB/s; divisions gone: 0.67 ms (not the arithmetic);
 // one work-group per (row, slice) with the per-image factors in LDS and one wide tmax load: 0.52 ms (276 k work-groups living ~4 us
-// each: launch- and latency-bound); this form: see DESIGN_APPENDIX.md section 3.  Rows of padding tokens and the padding columns are written as zeros.
+// each: launch- and latency-bound); this form: see DESIGN_APPENDIX.md section 3.  Rows of padding tokens and the padding columns [yc ni, pcols) are written as
+// zeros; columns [pcols, ldp) of the row stride are not touched.
 constexpr int ROUTE_MAX_IMG = 2050;                             // images a 2048-column slice can touch (ni >= 1)
 constexpr int ROUTE_KM_ENTRIES = 16384;                         // staged kmax entries per batch of rows (32 KiB)
 constexpr int ROUTE_LDS_BYTES = ROUTE_MAX_IMG * 8 + ROUTE_KM_ENTRIES * 2 + 16;
 
 template <typename T>
-__global__ __launch_bounds__(256) void filip_route_kernel(T* __restrict__ P, long ldp, const unsigned char* __restrict__ mask,
+__global__ __launch_bounds__(256) void filip_route_kernel(T* __restrict__ P, long ldp, long pcols, const unsigned char* __restrict__ mask,
                                                           const float* __restrict__ log_temp, const float* __restrict__ g1,
                                                           const float* __restrict__ g2, long ldg, const short* __restrict__ kmax,
                                                           const short* __restrict__ tmax, const float* __restrict__ cnt, int bx, int nt,
@@ -249,7 +250,7 @@ __global__ __launch_bounds__(256) void filip_route_kernel(T* __restrict__ P, lon
     float* const s_a1 = reinterpret_cast<float*>(lds);           // [count] temp g1[x, y] / cnt[x]
     float* const s_a2 = s_a1 + ROUTE_MAX_IMG;                    // [count] temp g2[x, y] / ni
     short* const s_km = reinterpret_cast<short*>(s_a2 + ROUTE_MAX_IMG);   // [rows of the batch][count]
-    const int nch = (int)(ldp / VEC);
+    const int nch = (int)(pcols / VEC);                           // chunks written per row: the chunk's columns + its zero padding
     const int ch = blockIdx.x * 256 + threadIdx.x;
     const int x = blockIdx.y;
     const int ncols = yc * ni;

@@ -249,9 +249,10 @@ __global__ __launch_bounds__(256) void copy_rows_kernel(const T* __restrict__ sr
     }
 }
 
-// out[r, :] = a[r, :] + b[r, :]  (contiguous [rows, D]; sums gradient blocks of views that feed several pairs)
+// out[r, :] = a[r, :] + b[r, :]  (contiguous [rows, D]; sums gradient blocks of views that feed several pairs).  n16 whole 16-byte
+// chunks, then the n - n16 * VEC elements of a count that is no chunk multiple one by one (the first work-group's first lanes)
 template <typename T>
-__global__ __launch_bounds__(256) void add_rows_kernel(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ out, long n16) {
+__global__ __launch_bounds__(256) void add_rows_kernel(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ out, long n16, long n) {
     constexpr int VEC = Elem<T>::VEC;
     for (long id = (long)blockIdx.x * blockDim.x + threadIdx.x; id < n16; id += (long)gridDim.x * blockDim.x) {
         float x[VEC], y[VEC];
@@ -261,6 +262,8 @@ __global__ __launch_bounds__(256) void add_rows_kernel(const T* __restrict__ a, 
         for (int k = 0; k < VEC; ++k) x[k] += y[k];
         store_vec<T>(out + id * VEC, x);
     }
+    const long tail = n16 * VEC + threadIdx.x;
+    if (blockIdx.x == 0 && threadIdx.x < VEC && tail < n) out[tail] = from_f32<T>(to_f32(a[tail]) + to_f32(b[tail]));
 }
 
 // ---- row scatter-add / column sum (patch-embed bias and position-table gradients, x_clip.py:358,382-383) ----

@@ -672,15 +672,16 @@ int xclip_copy_rows(const void* src, int64_t lds, void* dst, int64_t ldd, int64_
 
 int xclip_add(const void* a, const void* b, void* out, int64_t count, int dtype, void* stream) {
     XC_REQUIRE(dtype_ok(dtype), "bad dtype");
-    XC_REQUIRE(count % vec_of(dtype) == 0 && aligned16(a) && aligned16(b) && aligned16(out), "count must be a chunk multiple, 16-byte aligned");
+    XC_REQUIRE(count >= 0 && aligned16(a) && aligned16(b) && aligned16(out), "pointers must be 16-byte aligned");
     if (count == 0) return 0;
     const int64_t n16 = count / vec_of(dtype);
     int64_t blocks = (n16 + 255) / 256;
     if (blocks > 4096) blocks = 4096;
+    if (blocks < 1) blocks = 1;                                      // (a count below one chunk: the scalar tail alone)
     if (dtype == XCLIP_BF16)
-        hipLaunchKernelGGL((add_rows_kernel<bf16_t>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, (long)n16);
+        hipLaunchKernelGGL((add_rows_kernel<bf16_t>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, (long)n16, (long)count);
     else
-        hipLaunchKernelGGL((add_rows_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)a, (const float*)b, (float*)out, (long)n16);
+        hipLaunchKernelGGL((add_rows_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)a, (const float*)b, (float*)out, (long)n16, (long)count);
     return check_launch(__func__);
 }
 
@@ -1325,22 +1326,23 @@ int xclip_filip_fused_fwd(const void* X, const uint8_t* mask, const void* Y, con
     return check_launch(__func__);
 }
 
-int xclip_filip_route(void* P, int64_t ldp, const uint8_t* mask, const float* log_temp, const float* g1, const float* g2, int64_t ldg,
+int xclip_filip_route(void* P, int64_t ldp, int64_t pcols, const uint8_t* mask, const float* log_temp, const float* g1, const float* g2, int64_t ldg,
                       const int16_t* kmax, const int16_t* tmax, const float* cnt, int64_t bx, int64_t nt, int64_t yc, int64_t ni,
                       int64_t y0, int64_t ytotal, int dtype, void* stream) {
     XC_REQUIRE(dtype_ok(dtype), "bad dtype");
     XC_REQUIRE(bx > 0 && nt > 0 && yc > 0 && ni > 0, "bad shape");
-    XC_REQUIRE(ldp % vec_of(dtype) == 0 && ldp >= yc * ni && aligned16(P), "ldp must cover a chunk row, 16-byte chunk aligned");
+    XC_REQUIRE(ldp % vec_of(dtype) == 0 && pcols % vec_of(dtype) == 0 && pcols >= yc * ni && ldp >= pcols && aligned16(P),
+               "pcols must cover a chunk row and ldp pcols, both 16-byte chunk aligned");
     XC_REQUIRE(P && mask && log_temp && g1 && g2 && kmax && tmax && cnt, "null pointer");
-    XC_REQUIRE(bx * nt < (1LL << 31) && ldp / vec_of(dtype) < (1LL << 31) && bx <= 65535, "chunk too large for the launch grid");
+    XC_REQUIRE(bx * nt < (1LL << 31) && pcols / vec_of(dtype) < (1LL << 31) && bx <= 65535, "chunk too large for the launch grid");
     // one work-group per (text x, slice of 256 chunks): blockIdx.y = x
-    dim3 grid((unsigned)((ldp / vec_of(dtype) + 255) / 256), (unsigned)bx), block(256);
+    dim3 grid((unsigned)((pcols / vec_of(dtype) + 255) / 256), (unsigned)bx), block(256);
     if (dtype == XCLIP_BF16) {
         XC_ALLOW_LDS((filip_route_kernel<bf16_t>), ROUTE_LDS_BYTES);
-        hipLaunchKernelGGL((filip_route_kernel<bf16_t>), grid, block, ROUTE_LDS_BYTES, (hipStream_t)stream, (bf16_t*)P, (long)ldp, mask, log_temp, g1, g2, (long)ldg, kmax, tmax, cnt, (int)bx, (int)nt, (int)yc, (int)ni, (int)y0, (int)ytotal);
+        hipLaunchKernelGGL((filip_route_kernel<bf16_t>), grid, block, ROUTE_LDS_BYTES, (hipStream_t)stream, (bf16_t*)P, (long)ldp, (long)pcols, mask, log_temp, g1, g2, (long)ldg, kmax, tmax, cnt, (int)bx, (int)nt, (int)yc, (int)ni, (int)y0, (int)ytotal);
     } else {
         XC_ALLOW_LDS((filip_route_kernel<float>), ROUTE_LDS_BYTES);
-        hipLaunchKernelGGL((filip_route_kernel<float>), grid, block, ROUTE_LDS_BYTES, (hipStream_t)stream, (float*)P, (long)ldp, mask, log_temp, g1, g2, (long)ldg, kmax, tmax, cnt, (int)bx, (int)nt, (int)yc, (int)ni, (int)y0, (int)ytotal);
+        hipLaunchKernelGGL((filip_route_kernel<float>), grid, block, ROUTE_LDS_BYTES, (hipStream_t)stream, (float*)P, (long)ldp, (long)pcols, mask, log_temp, g1, g2, (long)ldg, kmax, tmax, cnt, (int)bx, (int)nt, (int)yc, (int)ni, (int)y0, (int)ytotal);
     }
     return check_launch(__func__);
 }

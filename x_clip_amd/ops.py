@@ -646,8 +646,10 @@ def bmm(a: Tensor, b: Tensor, M: int, N: int, K: int, a_kmajor: bool = False, b_
 def rowdot(a: Tensor, b: Tensor) -> Tensor:
     """out[r] = <a[r], b[r]> for a, b [rows, d] (einsum('b d, b d -> b'), x_clip.py:744-746)"""
     _dev_check(a, b)
-    a, b = _c(a), _c(b)
     assert a.shape == b.shape and a.dim() == 2 and a.dtype == b.dtype
+    # a row-strided view is read in place when the library can (rows on 16-byte chunks); anything else is copied
+    v = vec(a.dtype)
+    a, b = (t if (t.stride(1) == 1 and t.stride(0) % v == 0 and t.data_ptr() % 16 == 0) else t.contiguous() for t in (a, b))
     out = torch.empty(a.shape[0], dtype=a.dtype, device=a.device)
     _lib.check(_lib.lib().xclip_rowdot(a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), out.data_ptr(), a.shape[0], a.shape[1],
                                        dtype_code(a), _stream(a)), "xclip_rowdot")
@@ -1033,12 +1035,13 @@ def filip_fused_fwd(X: Tensor, mask: Tensor, Y: Tensor, log_temp: Tensor, t2i: T
 
 def filip_route(P: Tensor, mask: Tensor, log_temp: Tensor, g1: Tensor, g2: Tensor, kmax: Tensor, tmax: Tensor, cnt: Tensor,
                 nt: int, ni: int, yc: int, y0: int):
-    """fills the chunk P [bx*nt, ldp] of d loss / d (token similarity) for image columns [y0, y0+yc)"""
+    """fills the chunk P [bx*nt, >= yc*ni] of d loss / d (token similarity) for image columns [y0, y0+yc); columns behind yc*ni up to P's
+    own width are written as zeros, nothing behind that width (P may be a column view of a wider buffer)"""
     _dev_check(P, mask, log_temp, g1, g2, kmax, tmax, cnt)
     bx = mask.shape[0]
     ytotal = g1.shape[1]
     assert P.dim() == 2 and P.stride(1) == 1 and P.shape[0] == bx * nt and g1.is_contiguous() and g2.is_contiguous()
-    _lib.check(_lib.lib().xclip_filip_route(P.data_ptr(), P.stride(0), mask.data_ptr(), log_temp.data_ptr(), g1.data_ptr(),
+    _lib.check(_lib.lib().xclip_filip_route(P.data_ptr(), P.stride(0), P.shape[1], mask.data_ptr(), log_temp.data_ptr(), g1.data_ptr(),
                                             g2.data_ptr(), ytotal, kmax.data_ptr(), tmax.data_ptr(), cnt.data_ptr(), bx, nt, yc, ni, y0,
                                             ytotal, dtype_code(P), _stream(P)), "xclip_filip_route")
 
@@ -1053,12 +1056,16 @@ def rowlse(S: Tensor, diag_off: int, dcl: bool, coef: float, loss_accum: Optiona
     return lse
 
 
-def rowgrad(S: Tensor, lse: Tensor, diag_off: int, dcl: bool, coef: float, gmul: Optional[Tensor], dtau_accum: Optional[Tensor]) -> Tensor:
-    _dev_check(S, lse, gmul, dtau_accum)
+def rowgrad(S: Tensor, lse: Tensor, diag_off: int, dcl: bool, coef: float, gmul: Optional[Tensor], dtau_accum: Optional[Tensor],
+            out: Optional[Tensor] = None) -> Tensor:
+    """out: an fp32 [rows, cols] destination with unit inner stride (a column view of a wider buffer is fine: nothing behind `cols` is written)"""
+    _dev_check(S, lse, gmul, dtau_accum, out)
+    assert S.dim() == 2 and S.dtype == torch.float32 and S.stride(1) == 1
     rows, cols = S.shape
-    G = torch.empty(rows, cols, dtype=torch.float32, device=S.device)
+    G = torch.empty(rows, cols, dtype=torch.float32, device=S.device) if out is None else out
+    assert G.dtype == torch.float32 and tuple(G.shape) == (rows, cols) and G.stride(1) == 1
     _lib.check(_lib.lib().xclip_rowgrad(S.data_ptr(), S.stride(0), lse.data_ptr(), rows, cols, diag_off, int(dcl), coef, _ptr(gmul),
-                                        G.data_ptr(), cols, _ptr(dtau_accum), _stream(S)), "xclip_rowgrad")
+                                        G.data_ptr(), G.stride(0), _ptr(dtau_accum), _stream(S)), "xclip_rowgrad")
     return G
 
 
