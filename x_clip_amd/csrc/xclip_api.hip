@@ -65,10 +65,13 @@ inline int chunks_per_lane(int64_t dim, int vec) {
 constexpr int ROWS_NT = 1 | 2 | 4 | 8 | 32;
 inline bool rows_nt_flipped(int bit) { return ((measure_env("XCLIP_ROWS_NT", ROWS_NT) ^ ROWS_NT) & bit) != 0; }
 
+struct LnFwdArgs {                                            // xclip_layernorm_fwd's arguments, in its order
+    const void* x; int64_t ldx; const void* g; const void* res; void* y; int64_t ldy; int y_grp;
+    float* mean; float* rstd; int rows, dim; float eps; int geglu;
+};
 template <typename T, int MAXC>
-void launch_ln_fwd(const void* x, int64_t ldx, const void* g, const void* res, void* y, int64_t ldy, int y_grp, float* mean,
-                   float* rstd, int rows, int dim, float eps, int geglu, hipStream_t st) {
-    dim3 grid((rows + 3) / 4), block(256);
+void launch_ln_fwd(const LnFwdArgs& a, hipStream_t st) {
+    dim3 grid((a.rows + 3) / 4), block(256);
 #ifdef XCLIP_MEASURE
     if constexpr (MAXC <= 2) {
         // measured and not kept (profiles/r03_k_ln_fwd_rows_per_wave.log): several rows per wave with all loads ahead of the reductions
@@ -76,8 +79,8 @@ void launch_ln_fwd(const void* x, int64_t ldx, const void* g, const void* res, v
         // 117 us; with the residual 137 against 141 / 147 / 168 us; 1.18 M x 1024: 796 (6.1 TB/s) against 904 / 1000 / 1514 us.  The
         // one-row kernel is at the copy ceiling when it runs alone; its lower in-step figure is not a property of the kernel.
         static const int rpw = measure_env("XCLIP_LN_FWD", 0);
-        if (!geglu && rpw > 0) {
-#define XC_LNR(R) { dim3 g2((rows + 4 * R - 1) / (4 * R)); hipLaunchKernelGGL((ln_fwd_rows_kernel<T, MAXC, R>), g2, block, 0, st, (const T*)x, (long)ldx, (const T*)g, (const T*)res, (T*)y, mean, rstd, rows, dim, eps, (long)ldy, y_grp); return; }
+        if (!a.geglu && rpw > 0) {
+#define XC_LNR(R) { dim3 g2((a.rows + 4 * R - 1) / (4 * R)); hipLaunchKernelGGL((ln_fwd_rows_kernel<T, MAXC, R>), g2, block, 0, st, (const T*)a.x, (long)a.ldx, (const T*)a.g, (const T*)a.res, (T*)a.y, a.mean, a.rstd, a.rows, a.dim, a.eps, (long)a.ldy, a.y_grp); return; }
             if (rpw == 1) XC_LNR(1)
             if (rpw == 4) XC_LNR(4)
             XC_LNR(2)
@@ -86,26 +89,16 @@ void launch_ln_fwd(const void* x, int64_t ldx, const void* g, const void* res, v
     }
 #endif
     constexpr bool NTG = (ROWS_NT & 2) != 0, NTP = (ROWS_NT & 4) != 0;
+#define XC_LNF(KERNEL) hipLaunchKernelGGL(KERNEL, grid, block, 0, st, (const T*)a.x, (long)a.ldx, (const T*)a.g, (const T*)a.res, (T*)a.y, a.mean, a.rstd, a.rows, a.dim, a.eps, (long)a.ldy, a.y_grp)
 #ifdef XCLIP_MEASURE
     if constexpr (sizeof(T) == 2 && MAXC <= 4) {
-        if (geglu && rows_nt_flipped(2)) {
-            hipLaunchKernelGGL((ln_fwd_kernel<T, MAXC, true, !NTG>), grid, block, 0, st, (const T*)x, (long)ldx, (const T*)g, (const T*)res,
-                               (T*)y, mean, rstd, rows, dim, eps, (long)ldy, y_grp);
-            return;
-        }
-        if (!geglu && rows_nt_flipped(4)) {
-            hipLaunchKernelGGL((ln_fwd_kernel<T, MAXC, false, !NTP>), grid, block, 0, st, (const T*)x, (long)ldx, (const T*)g, (const T*)res,
-                               (T*)y, mean, rstd, rows, dim, eps, (long)ldy, y_grp);
-            return;
-        }
+        if (a.geglu && rows_nt_flipped(2)) { XC_LNF((ln_fwd_kernel<T, MAXC, true, !NTG>)); return; }
+        if (!a.geglu && rows_nt_flipped(4)) { XC_LNF((ln_fwd_kernel<T, MAXC, false, !NTP>)); return; }
     }
 #endif
-    if (geglu)
-        hipLaunchKernelGGL((ln_fwd_kernel<T, MAXC, true, NTG>), grid, block, 0, st, (const T*)x, (long)ldx, (const T*)g, (const T*)res,
-                           (T*)y, mean, rstd, rows, dim, eps, (long)ldy, y_grp);
-    else
-        hipLaunchKernelGGL((ln_fwd_kernel<T, MAXC, false, NTP>), grid, block, 0, st, (const T*)x, (long)ldx, (const T*)g,
-                           (const T*)res, (T*)y, mean, rstd, rows, dim, eps, (long)ldy, y_grp);
+    if (a.geglu) XC_LNF((ln_fwd_kernel<T, MAXC, true, NTG>));
+    else XC_LNF((ln_fwd_kernel<T, MAXC, false, NTP>));
+#undef XC_LNF
 }
 constexpr int LN_BWD_MAX_BLOCKS = 4096;          // MI355X, 263k x 512 rows: 1024 work-groups 180 us, 2048: 189, 4096: 163, 8192: 165
 inline int ln_bwd_blocks(int64_t rows) {
@@ -122,24 +115,27 @@ inline int ln_geglu_bwd_blocks(int64_t rows) {
     return (int)(b < want ? (b < 1 ? 1 : b) : want);
 }
 
+struct LnBwdArgs {                                            // xclip_layernorm_bwd's operands; dg: the rows of partial gain gradients
+    const void* dy; const void* x; int64_t ldx; const void* g; const float* mean; const float* rstd;
+    const void* dres; void* dx; int64_t lddx; float* dg; int rows, dim, geglu;
+};
 template <typename T, int MAXC>
-int launch_ln_bwd(const void* dy, const void* x, int64_t ldx, const void* g, const float* mean, const float* rstd,
-                  const void* dres, void* dx, int64_t lddx, float* dg, int rows, int dim, int geglu, hipStream_t st) {
-    const int blocks = ln_bwd_blocks(rows);
+int launch_ln_bwd(const LnBwdArgs& a, hipStream_t st) {
+    const int blocks = ln_bwd_blocks(a.rows);
     dim3 grid(blocks), block(256);
-    const size_t lds = (size_t)3 * dim * sizeof(float);
+    const size_t lds = (size_t)3 * a.dim * sizeof(float);
     constexpr bool NTG = (ROWS_NT & 1) != 0, NTP = (ROWS_NT & 8) != 0;
-#define XC_LNB(KERNEL, GRID, LDS) do { XC_ALLOW_LDS((KERNEL), LDS); hipLaunchKernelGGL((KERNEL), GRID, block, LDS, st, (const T*)dy, (const T*)x, (long)ldx, (const T*)g, mean, rstd, (T*)dx, (long)lddx, dg, rows, dim); } while (0)
-#define XC_LNB_RES(KERNEL, GRID, LDS) do { XC_ALLOW_LDS((KERNEL), LDS); hipLaunchKernelGGL((KERNEL), GRID, block, LDS, st, (const T*)dy, (const T*)x, (long)ldx, (const T*)g, mean, rstd, (const T*)dres, (T*)dx, (long)lddx, dg, rows, dim); } while (0)
-    if (geglu) {
+#define XC_LNB(KERNEL, GRID, LDS) do { XC_ALLOW_LDS((KERNEL), LDS); hipLaunchKernelGGL((KERNEL), GRID, block, LDS, st, (const T*)a.dy, (const T*)a.x, (long)a.ldx, (const T*)a.g, a.mean, a.rstd, (T*)a.dx, (long)a.lddx, a.dg, a.rows, a.dim); } while (0)
+#define XC_LNB_RES(KERNEL, GRID, LDS) do { XC_ALLOW_LDS((KERNEL), LDS); hipLaunchKernelGGL((KERNEL), GRID, block, LDS, st, (const T*)a.dy, (const T*)a.x, (long)a.ldx, (const T*)a.g, a.mean, a.rstd, (const T*)a.dres, (T*)a.dx, (long)a.lddx, a.dg, a.rows, a.dim); } while (0)
+    if (a.geglu) {
         // rows wider than 3 chunks per lane are shared by two waves (register budget: three waves per SIMD)
         constexpr int SPLIT = (MAXC >= 4 && MAXC % 2 == 0) ? 2 : 1;
         constexpr int C = MAXC / SPLIT;
-        const bool split = SPLIT == 2 && (dim / Elem<T>::VEC) % 2 == 0;
+        const bool split = SPLIT == 2 && (a.dim / Elem<T>::VEC) % 2 == 0;
         // four waves' dg partials of their column part + the row sums + gamma
-        const size_t lds2 = ((size_t)4 * (dim / (split ? 2 : 1)) + 16) * sizeof(float) + (size_t)dim * sizeof(T)
-                            + (measure_env("XCLIP_LNG_LDSPAD", 0) && split ? (size_t)2 * dim * sizeof(float) : 0);   // what rounds 1-3 requested
-        dim3 ggrid(ln_geglu_bwd_blocks(rows));
+        const size_t lds2 = ((size_t)4 * (a.dim / (split ? 2 : 1)) + 16) * sizeof(float) + (size_t)a.dim * sizeof(T)
+                            + (measure_env("XCLIP_LNG_LDSPAD", 0) && split ? (size_t)2 * a.dim * sizeof(float) : 0);   // what rounds 1-3 requested
+        dim3 ggrid(ln_geglu_bwd_blocks(a.rows));
         if (split) {
 #ifdef XCLIP_MEASURE
             if (rows_nt_flipped(1)) {
@@ -195,11 +191,33 @@ int launch_ln_bwd(const void* dy, const void* x, int64_t ldx, const void* g, con
         }                                                                \
     } while (0)
 
-template <typename T, bool AK, bool BK_>
-void launch_gemm(const GemmParams& p, int splits, hipStream_t st) {
-    XC_ALLOW_LDS((gemm_kernel<T, AK, BK_>), GemmCfg<T>::LDS_BYTES);
-    dim3 grid(p.tiles_m * p.tiles_n, splits), block(GEMM_THREADS);
-    hipLaunchKernelGGL((gemm_kernel<T, AK, BK_>), grid, block, GemmCfg<T>::LDS_BYTES, st, p);
+// the three operand layouts in use as template arguments (api_common.h by_dtype): NT (false, false), NN (false, true), TN (true, true);
+// (A k-major, B normal) is refused by the entry points and never instantiated
+template <typename F> inline void by_layout(int a_kmajor, int b_kmajor, F&& f) {
+    if (!a_kmajor && !b_kmajor) f(bool_tag<false>{}, bool_tag<false>{});
+    else if (!a_kmajor) f(bool_tag<false>{}, bool_tag<true>{});
+    else f(bool_tag<true>{}, bool_tag<true>{});
+}
+
+// the generic 128 x 128 kernel (gemm.h): grid.y = K slices, grid.z = problems of a batch
+void launch_gemm(const GemmParams& p, int dtype, int a_kmajor, int b_kmajor, int splits, int64_t batch, hipStream_t st) {
+    const dim3 grid(p.tiles_m * p.tiles_n, splits, (unsigned)batch), block(GEMM_THREADS);
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        by_layout(a_kmajor, b_kmajor, [&](auto ak, auto bk) {
+            constexpr bool AK = decltype(ak)::value, BK_ = decltype(bk)::value;
+            XC_ALLOW_LDS((gemm_kernel<T, AK, BK_>), GemmCfg<T>::LDS_BYTES);
+            hipLaunchKernelGGL((gemm_kernel<T, AK, BK_>), grid, block, GemmCfg<T>::LDS_BYTES, st, p);
+        });
+    });
+}
+// the fp32 slabs of a split-K product -> C = alpha * sum (+ residual: the row tail of a product with a skip term)
+template <typename T>
+void launch_splitk_reduce(const void* slabs, void* C, int64_t ldc, int64_t M, int64_t N, int splits, float alpha, const void* residual,
+                          int64_t ldr, hipStream_t st) {
+    int64_t blocks = (M * (N / 4) + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, st, (const float*)slabs, (T*)C, (long)ldc, (int)M, (int)N,
+                       splits, alpha, (const T*)residual, (long)ldr);
 }
 
 // Which bf16 GEMM runs.  Product (0): g5_run (A in a ring of three LDS stages) for the layouts whose B operand is a weight panel that
@@ -381,6 +399,57 @@ int gemm_splits(int64_t M, int64_t N, int64_t K, int dtype) {
     return s < 2 ? 1 : (int)s;
 }
 
+// ---- one plan per product: xclip_gemm executes it, xclip_gemm_workspace_bytes reports its bytes ----------------------------------------
+struct GemmArgs {                                             // xclip_gemm's arguments, in its order
+    int a_kmajor, b_kmajor;
+    const void* A; int64_t lda; const void* B; int64_t ldb; void* C; int64_t ldc;
+    int64_t M, N, K; float alpha;
+    const void* bias; const void* residual; int64_t ldr; const void* addrows; const int32_t* rowidx; int64_t ld_add;
+    void* workspace; int64_t workspace_bytes;
+};
+enum GemmRoute { GEMM_SMALL, GEMM_256, GEMM_256_CUT, GEMM_GENERIC };   // gemm_small.h; gemm2.h ... gemm8.h (launch_gemm2); the same, row tail cut; gemm.h
+struct GemmPlan {
+    GemmRoute route;
+    int splits, k_per_split;             // K slices (no empty ones) and their length; GEMM_256_CUT: of the tail (its main rows take one slice)
+    int64_t main_rows, tail_rows;        // GEMM_256_CUT: rows of the main launch, rows of the split-K tail behind it
+    int64_t workspace_bytes;             // the fp32 slabs the route wants; offered less, the product runs in one slice (and uncut)
+};
+// K in slices of whole `bk` steps: rounding the slice up can leave the last slices EMPTY (96 K steps over 17 slices -> 6 per slice, 16 slices
+// cover them): a slice without work returns without touching its slab and the reduction would add whatever the workspace held before
+inline void gemm_slices(GemmPlan& p, int s, int64_t K, int bk) {
+    p.k_per_split = K > 0 ? (int)((((K + s - 1) / s) + bk - 1) / bk * bk) : 0;   // (K <= 0: the size query of a shape xclip_gemm refuses --
+    p.splits = K > 0 ? (int)((K + p.k_per_split - 1) / p.k_per_split) : 1;       //  one slice of nothing)
+}
+// offer: the bytes of workspace at hand (0 without one); small_flop: the limit of the 64 x 64 kernel (xclip_gemm_small_limit)
+GemmPlan gemm_plan(const GemmArgs& g, int dtype, int64_t offer, int64_t small_flop) {
+    const int64_t M = g.M, N = g.N, K = g.K;
+    const bool bias_or_rows = g.bias != nullptr || g.addrows != nullptr, plain = !bias_or_rows && g.residual == nullptr;
+    GemmPlan p{};                                             // (route GEMM_SMALL)
+    if (dtype == XCLIP_BF16 && gs_takes(M, N, K, bias_or_rows, g.lda, g.ldb, small_flop)) return p;      // GEMM_SMALL, no workspace
+    const bool g2 = use_gemm2(M, N, K, dtype);
+    p.route = g2 ? GEMM_256 : GEMM_GENERIC;
+    const int bk = g2 ? G2_BK : 8 * vec_of(dtype);
+    // the row tail as a split-K problem of its own (gemm2_tail_cut): normal-A layouts, no bias / gathered rows (the reduction adds the skip term)
+    const int64_t cut = (g2 && !g.a_kmajor && !bias_or_rows) ? gemm2_tail_cut(M, N, K) : 0;
+    if (cut > 0) {
+        const int ts = gemm2_splits(M - cut, N, K);
+        p.workspace_bytes = (int64_t)ts * (M - cut) * N * 4;
+        if (ts > 1 && offer >= p.workspace_bytes) {
+            gemm_slices(p, ts, K, bk);
+            if (p.splits > 1) {                                 // (always: ts slices of >= 4 K steps each stay >= 2 after the rounding)
+                p.route = GEMM_256_CUT;
+                p.main_rows = cut; p.tail_rows = M - cut;
+                return p;
+            }
+        }
+    }
+    int s = g2 ? gemm2_splits(M, N, K) : gemm_splits(M, N, K, dtype);
+    if (cut == 0) p.workspace_bytes = s > 1 ? (int64_t)s * M * N * 4 : 0;
+    if (s > 1 && (!plain || offer < (int64_t)s * M * N * 4)) s = 1;       // a short or missing workspace: one slice
+    gemm_slices(p, s, K, bk);
+    return p;
+}
+
 }  // namespace
 
 extern "C" {
@@ -402,7 +471,8 @@ int xclip_layernorm_fwd(const void* x, int64_t ldx, const void* g, const void* r
     XC_REQUIRE(aligned16(x) && aligned16(g) && aligned16(y) && aligned16(res), "pointers must be 16-byte aligned");
     if (rows == 0) return 0;
     const int cpl = chunks_per_lane(dim, vec);
-#define F(T, C) launch_ln_fwd<T, C>(x, ldx, g, res, y, ldy, (int)y_grp, mean, rstd, (int)rows, (int)dim, eps, geglu, (hipStream_t)stream)
+    const LnFwdArgs a{x, ldx, g, res, y, ldy, (int)y_grp, mean, rstd, (int)rows, (int)dim, eps, geglu};
+#define F(T, C) launch_ln_fwd<T, C>(a, (hipStream_t)stream)
     XC_DISPATCH_ROW(dtype, cpl, F);
 #undef F
     return check_launch(__func__);
@@ -425,7 +495,8 @@ int xclip_layernorm_bwd(const void* dy, const void* x, int64_t ldx, const void* 
     const int cpl = chunks_per_lane(dim, vec);
     float* partial = (float*)workspace;
     int nblk = 0;                                              // rows of dg partials the kernel wrote
-#define F(T, C) nblk = launch_ln_bwd<T, C>(dy, x, ldx, g, mean, rstd, dres, dx, lddx, partial, (int)rows, (int)dim, geglu, (hipStream_t)stream)
+    const LnBwdArgs a{dy, x, ldx, g, mean, rstd, dres, dx, lddx, partial, (int)rows, (int)dim, geglu};
+#define F(T, C) nblk = launch_ln_bwd<T, C>(a, (hipStream_t)stream)
     XC_DISPATCH_ROW(dtype, cpl, F);
 #undef F
     int slices = nblk / 64;
@@ -563,14 +634,11 @@ int xclip_text_embed_fwd(const int64_t* tokens, const void* E, const void* P, co
     const int64_t rows = batch * (n + (cls ? 1 : 0));
     if (rows == 0) return 0;
     dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-    if (dtype == XCLIP_BF16)
-        hipLaunchKernelGGL((text_embed_fwd_kernel<bf16_t>), grid, block, 0, (hipStream_t)stream, (const long long*)tokens,
-                           (const bf16_t*)E, (const bf16_t*)P, (const bf16_t*)cls, (bf16_t*)out, (int)batch, (int)n, (int)dim,
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((text_embed_fwd_kernel<T>), grid, block, 0, (hipStream_t)stream, (const long long*)tokens,
+                           (const T*)E, (const T*)P, (const T*)cls, (T*)out, (int)batch, (int)n, (int)dim,
                            (long long)vocab, bad_token_flag);
-    else
-        hipLaunchKernelGGL((text_embed_fwd_kernel<float>), grid, block, 0, (hipStream_t)stream, (const long long*)tokens,
-                           (const float*)E, (const float*)P, (const float*)cls, (float*)out, (int)batch, (int)n, (int)dim,
-                           (long long)vocab, bad_token_flag);
+    });
     return check_launch(__func__);
 }
 
@@ -613,12 +681,9 @@ int xclip_patchify(const void* image, const int32_t* keep, void* out, int64_t ld
                            (bf16_t*)out, (long)ldo, (int)batch, (int)height, (int)width, (int)patch, (int)nkeep);
         return check_launch(__func__);
     }
-    if (dtype == XCLIP_BF16)
-        hipLaunchKernelGGL((patchify_kernel<bf16_t>), grid, block, 0, (hipStream_t)stream, (const bf16_t*)image, (const int*)keep,
-                           (bf16_t*)out, (long)ldo, (int)batch, (int)channels, (int)height, (int)width, (int)patch, (int)nkeep);
-    else
-        hipLaunchKernelGGL((patchify_kernel<float>), grid, block, 0, (hipStream_t)stream, (const float*)image, (const int*)keep,
-                           (float*)out, (long)ldo, (int)batch, (int)channels, (int)height, (int)width, (int)patch, (int)nkeep);
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((patchify_kernel<T>), grid, block, 0, (hipStream_t)stream, (const T*)image, (const int*)keep, (T*)out, (long)ldo, (int)batch, (int)channels, (int)height, (int)width, (int)patch, (int)nkeep);
+    });
     return check_launch(__func__);
 }
 
@@ -631,10 +696,9 @@ int xclip_token_mean_fwd(const void* x, int64_t x_batch_stride, void* out, int64
     XC_REQUIRE(aligned16(x) && aligned16(out), "pointers must be 16-byte aligned");
     if (batch == 0) return 0;
     dim3 grid((unsigned)batch, (unsigned)((dim / vec + 63) / 64)), block(64);
-    if (dtype == XCLIP_BF16)
-        hipLaunchKernelGGL((token_mean_fwd_kernel<bf16_t>), grid, block, 0, (hipStream_t)stream, (const bf16_t*)x, (long)x_batch_stride, (bf16_t*)out, (int)n, (int)dim);
-    else
-        hipLaunchKernelGGL((token_mean_fwd_kernel<float>), grid, block, 0, (hipStream_t)stream, (const float*)x, (long)x_batch_stride, (float*)out, (int)n, (int)dim);
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((token_mean_fwd_kernel<T>), grid, block, 0, (hipStream_t)stream, (const T*)x, (long)x_batch_stride, (T*)out, (int)n, (int)dim);
+    });
     return check_launch(__func__);
 }
 
@@ -647,10 +711,9 @@ int xclip_token_mean_bwd(const void* dout, const void* dsrc, int64_t src_batch_s
     XC_REQUIRE(aligned16(dout) && aligned16(dx) && aligned16(dsrc), "pointers must be 16-byte aligned");
     if (batch == 0) return 0;
     dim3 grid((unsigned)((batch * n + 3) / 4)), block(256);
-    if (dtype == XCLIP_BF16)
-        hipLaunchKernelGGL((token_mean_bwd_kernel<bf16_t>), grid, block, 0, (hipStream_t)stream, (const bf16_t*)dout, (const bf16_t*)dsrc, (long)src_batch_stride, (bf16_t*)dx, (int)batch, (int)n, (int)dim);
-    else
-        hipLaunchKernelGGL((token_mean_bwd_kernel<float>), grid, block, 0, (hipStream_t)stream, (const float*)dout, (const float*)dsrc, (long)src_batch_stride, (float*)dx, (int)batch, (int)n, (int)dim);
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((token_mean_bwd_kernel<T>), grid, block, 0, (hipStream_t)stream, (const T*)dout, (const T*)dsrc, (long)src_batch_stride, (T*)dx, (int)batch, (int)n, (int)dim);
+    });
     return check_launch(__func__);
 }
 
@@ -663,10 +726,9 @@ int xclip_copy_rows(const void* src, int64_t lds, void* dst, int64_t ldd, int64_
     int64_t blocks = (rows * (dim / vec) + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     dim3 grid((unsigned)blocks), block(256);
-    if (dtype == XCLIP_BF16)
-        hipLaunchKernelGGL((copy_rows_kernel<bf16_t>), grid, block, 0, (hipStream_t)stream, (const bf16_t*)src, (long)lds, (bf16_t*)dst, (long)ldd, (long)rows, (int)dim);
-    else
-        hipLaunchKernelGGL((copy_rows_kernel<float>), grid, block, 0, (hipStream_t)stream, (const float*)src, (long)lds, (float*)dst, (long)ldd, (long)rows, (int)dim);
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((copy_rows_kernel<T>), grid, block, 0, (hipStream_t)stream, (const T*)src, (long)lds, (T*)dst, (long)ldd, (long)rows, (int)dim);
+    });
     return check_launch(__func__);
 }
 
@@ -678,10 +740,9 @@ int xclip_add(const void* a, const void* b, void* out, int64_t count, int dtype,
     int64_t blocks = (n16 + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;                                      // (a count below one chunk: the scalar tail alone)
-    if (dtype == XCLIP_BF16)
-        hipLaunchKernelGGL((add_rows_kernel<bf16_t>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, (long)n16, (long)count);
-    else
-        hipLaunchKernelGGL((add_rows_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)a, (const float*)b, (float*)out, (long)n16, (long)count);
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((add_rows_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const T*)a, (const T*)b, (T*)out, (long)n16, (long)count);
+    });
     return check_launch(__func__);
 }
 
@@ -783,10 +844,9 @@ int xclip_cast_from_f32(const float* src, void* dst, int64_t count, float scale,
     int64_t blocks = (count + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     dim3 grid((unsigned)blocks), block(256);
-    if (dtype == XCLIP_BF16)
-        hipLaunchKernelGGL((cast_from_f32_kernel<bf16_t>), grid, block, 0, (hipStream_t)stream, src, (bf16_t*)dst, (long)count, scale);
-    else
-        hipLaunchKernelGGL((cast_from_f32_kernel<float>), grid, block, 0, (hipStream_t)stream, src, (float*)dst, (long)count, scale);
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((cast_from_f32_kernel<T>), grid, block, 0, (hipStream_t)stream, src, (T*)dst, (long)count, scale);
+    });
     return check_launch(__func__);
 }
 
@@ -815,10 +875,9 @@ int xclip_dwconv4s2_fwd(const void* x, const void* w, void* y, int64_t batch, in
     int64_t blocks = (items + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     dim3 grid((unsigned)blocks), block(256);
-    if (dtype == XCLIP_BF16)
-        hipLaunchKernelGGL((dwconv_fwd_kernel<bf16_t>), grid, block, 0, (hipStream_t)stream, (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, (int)batch, (int)h, (int)C);
-    else
-        hipLaunchKernelGGL((dwconv_fwd_kernel<float>), grid, block, 0, (hipStream_t)stream, (const float*)x, (const float*)w, (float*)y, (int)batch, (int)h, (int)C);
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((dwconv_fwd_kernel<T>), grid, block, 0, (hipStream_t)stream, (const T*)x, (const T*)w, (T*)y, (int)batch, (int)h, (int)C);
+    });
     return check_launch(__func__);
 }
 int xclip_dwconv4s2_bwd(const void* dy, const void* x, const void* w, void* dx, float* dw_accum, void* workspace, int64_t workspace_bytes,
@@ -831,10 +890,9 @@ int xclip_dwconv4s2_bwd(const void* dy, const void* x, const void* w, void* dx, 
     const int blocks = dwconv_bwd_blocks(batch, h, C, dtype);
     dim3 grid((unsigned)blocks), block(256);
     float* partial = (float*)workspace;
-    if (dtype == XCLIP_BF16)
-        hipLaunchKernelGGL((dwconv_bwd_kernel<bf16_t>), grid, block, 0, (hipStream_t)stream, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)dx, partial, (int)batch, (int)h, (int)C);
-    else
-        hipLaunchKernelGGL((dwconv_bwd_kernel<float>), grid, block, 0, (hipStream_t)stream, (const float*)dy, (const float*)x, (const float*)w, (float*)dx, partial, (int)batch, (int)h, (int)C);
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((dwconv_bwd_kernel<T>), grid, block, 0, (hipStream_t)stream, (const T*)dy, (const T*)x, (const T*)w, (T*)dx, partial, (int)batch, (int)h, (int)C);
+    });
     hipLaunchKernelGGL(colsum_fold_kernel, dim3((unsigned)((C * 16 + 63) / 64), 4), dim3(256), 1024, (hipStream_t)stream,
                        (const float*)partial, (long)(C * 16), dw_accum, blocks * 4, (int)(C * 16));
     return check_launch(__func__);
@@ -848,10 +906,9 @@ int xclip_gather_rows(const void* src, int64_t lds, const int32_t* idx, void* ou
     int64_t blocks = (rows * (dim / vec_of(dtype)) + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     dim3 grid((unsigned)blocks), block(256);
-    if (dtype == XCLIP_BF16)
-        hipLaunchKernelGGL((gather_rows_kernel<bf16_t>), grid, block, 0, (hipStream_t)stream, (const bf16_t*)src, (long)lds, idx, (bf16_t*)out, (long)rows, (int)dim);
-    else
-        hipLaunchKernelGGL((gather_rows_kernel<float>), grid, block, 0, (hipStream_t)stream, (const float*)src, (long)lds, idx, (float*)out, (long)rows, (int)dim);
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((gather_rows_kernel<T>), grid, block, 0, (hipStream_t)stream, (const T*)src, (long)lds, idx, (T*)out, (long)rows, (int)dim);
+    });
     return check_launch(__func__);
 }
 int xclip_cross_entropy_fwd(const void* logits, int64_t ld, const int64_t* labels, int64_t rows, int64_t cols, float* lse, float* loss_accum,
@@ -863,10 +920,9 @@ int xclip_cross_entropy_fwd(const void* logits, int64_t ld, const int64_t* label
     int64_t blocks = (rows + 3) / 4;
     if (blocks > ROWLOSS_MAX_BLOCKS) blocks = ROWLOSS_MAX_BLOCKS;
     dim3 grid((unsigned)blocks), block(256);
-    if (dtype == XCLIP_BF16)
-        hipLaunchKernelGGL((ce_fwd_kernel<bf16_t>), grid, block, 16, (hipStream_t)stream, (const bf16_t*)logits, (long)ld, (const long long*)labels, (int)rows, (int)cols, lse, loss_accum);
-    else
-        hipLaunchKernelGGL((ce_fwd_kernel<float>), grid, block, 16, (hipStream_t)stream, (const float*)logits, (long)ld, (const long long*)labels, (int)rows, (int)cols, lse, loss_accum);
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((ce_fwd_kernel<T>), grid, block, 16, (hipStream_t)stream, (const T*)logits, (long)ld, (const long long*)labels, (int)rows, (int)cols, lse, loss_accum);
+    });
     return check_launch(__func__);
 }
 int xclip_cross_entropy_bwd(void* logits, int64_t ld, const int64_t* labels, const float* lse, const float* gmul, int64_t rows, int64_t cols,
@@ -876,10 +932,9 @@ int xclip_cross_entropy_bwd(void* logits, int64_t ld, const int64_t* labels, con
     if (rows == 0) return 0;                                  // (an empty tensor has a null data pointer)
     XC_REQUIRE(logits && labels && lse && gmul && aligned16(logits), "null or misaligned pointer");
     dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-    if (dtype == XCLIP_BF16)
-        hipLaunchKernelGGL((ce_bwd_kernel<bf16_t>), grid, block, 0, (hipStream_t)stream, (bf16_t*)logits, (long)ld, (const long long*)labels, lse, gmul, (int)rows, (int)cols);
-    else
-        hipLaunchKernelGGL((ce_bwd_kernel<float>), grid, block, 0, (hipStream_t)stream, (float*)logits, (long)ld, (const long long*)labels, lse, gmul, (int)rows, (int)cols);
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((ce_bwd_kernel<T>), grid, block, 0, (hipStream_t)stream, (T*)logits, (long)ld, (const long long*)labels, lse, gmul, (int)rows, (int)cols);
+    });
     return check_launch(__func__);
 }
 
@@ -892,10 +947,9 @@ int xclip_dropout(const void* x, void* y, int64_t n, float p, uint64_t seed, int
     if (blocks > 16384) blocks = 16384;
     const uint32_t th = drop_thresh(p);
     const float sc = 1.0f / (1.0f - p);
-    if (dtype == XCLIP_BF16)
-        hipLaunchKernelGGL((dropout_kernel<bf16_t>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, (long)n, th, sc, seed);
-    else
-        hipLaunchKernelGGL((dropout_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)x, (float*)y, (long)n, th, sc, seed);
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((dropout_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, (long)n, th, sc, seed);
+    });
     return check_launch(__func__);
 }
 
@@ -915,35 +969,30 @@ int xclip_rotary(void* x, int64_t ld, int64_t rows, int64_t n, int64_t slots, in
     if (rot != 32) {                                             // narrow heads: element pairs
         int64_t pb = (rows * slots * (rot / 2) + 255) / 256;
         if (pb > 8192) pb = 8192;
-        if (dtype == XCLIP_BF16)
-            hipLaunchKernelGGL((rotary_pairs_kernel<bf16_t>), dim3((unsigned)pb), block, 0, (hipStream_t)stream, (bf16_t*)x, (long)ld, (long)rows, (int)n, (int)slots, (int)slot_width, (int)(rot / 2), inv_freq, sign);
-        else
-            hipLaunchKernelGGL((rotary_pairs_kernel<float>), dim3((unsigned)pb), block, 0, (hipStream_t)stream, (float*)x, (long)ld, (long)rows, (int)n, (int)slots, (int)slot_width, (int)(rot / 2), inv_freq, sign);
+        by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+            hipLaunchKernelGGL((rotary_pairs_kernel<T>), dim3((unsigned)pb), block, 0, (hipStream_t)stream, (T*)x, (long)ld, (long)rows, (int)n, (int)slots, (int)slot_width, (int)(rot / 2), inv_freq, sign);
+        });
         return check_launch(__func__);
     }
-    if (dtype == XCLIP_BF16)
-        hipLaunchKernelGGL((rotary_kernel<bf16_t>), grid, block, 0, (hipStream_t)stream, (bf16_t*)x, (long)ld, (long)rows, (int)n, (int)slots, (int)slot_width, inv_freq, sign);
-    else
-        hipLaunchKernelGGL((rotary_kernel<float>), grid, block, 0, (hipStream_t)stream, (float*)x, (long)ld, (long)rows, (int)n, (int)slots, (int)slot_width, inv_freq, sign);
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((rotary_kernel<T>), grid, block, 0, (hipStream_t)stream, (T*)x, (long)ld, (long)rows, (int)n, (int)slots, (int)slot_width, inv_freq, sign);
+    });
     return check_launch(__func__);
 }
 
-// the 256 x 256 bf16 kernels behind xclip_gemm.  reduce = false: a split-K problem leaves its fp32 slabs in `workspace` for the caller
-// (*splits_out of them; alpha not applied).
-static int gemm2_run(int a_kmajor, int b_kmajor, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int64_t M, int64_t N,
-                     int64_t K, float alpha, const void* bias, const void* residual, int64_t ldr, const void* addrows, const int32_t* rowidx,
-                     int64_t ld_add, void* workspace, int64_t workspace_bytes, hipStream_t st, bool reduce, int* splits_out) {
-    const bool plain = (bias == nullptr && residual == nullptr && addrows == nullptr);
+// the 256 x 256 bf16 kernels behind xclip_gemm, on the plan's K slices.  reduce = false: a split-K problem leaves its fp32 slabs in
+// g.workspace for the caller (alpha not applied).
+static int gemm2_run(const GemmArgs& g, int splits, int k_per_split, bool reduce, hipStream_t st) {
     Gemm2Params q;
-    q.A = (const bf16_t*)A; q.B = (const bf16_t*)B; q.C = (bf16_t*)C; q.lda = lda; q.ldb = ldb; q.ldc = ldc;
-    q.M = (int)M; q.N = (int)N; q.K = (int)K; q.alpha = alpha;
-    q.bias = (const bf16_t*)bias; q.residual = (const bf16_t*)residual; q.ldr = ldr;
-    q.addrows = (const bf16_t*)addrows; q.rowidx = rowidx; q.ld_add = ld_add;
-    q.tiles_m = (int)((M + G2_BM - 1) / G2_BM); q.tiles_n = (int)((N + G2_BN - 1) / G2_BN);
+    q.A = (const bf16_t*)g.A; q.B = (const bf16_t*)g.B; q.C = (bf16_t*)g.C; q.lda = g.lda; q.ldb = g.ldb; q.ldc = g.ldc;
+    q.M = (int)g.M; q.N = (int)g.N; q.K = (int)g.K; q.alpha = g.alpha;
+    q.bias = (const bf16_t*)g.bias; q.residual = (const bf16_t*)g.residual; q.ldr = g.ldr;
+    q.addrows = (const bf16_t*)g.addrows; q.rowidx = g.rowidx; q.ld_add = g.ld_add;
+    q.tiles_m = (int)((g.M + G2_BM - 1) / G2_BM); q.tiles_n = (int)((g.N + G2_BN - 1) / G2_BN);
     // an output that cannot stay in the 8 x 4 MiB of L2 anyway is streamed past it: the A / B panels the sibling tiles share then
     // survive a round's 32 MiB of output (XCLIP_GEMM_NT=0 / 1 forces the policy, for measurement)
     static const int nt_env = measure_env("XCLIP_GEMM_NT", -1);
-    q.stream_out = nt_env >= 0 ? nt_env : (M * N * 2 > (int64_t)(48 << 20) ? 1 : 0);
+    q.stream_out = nt_env >= 0 ? nt_env : (g.M * g.N * 2 > (int64_t)(48 << 20) ? 1 : 0);
     // more than 8 N tiles (FF1: 16): banded tile order for the ring kernel (XCLIP_GEMM_BAND=<tiles per band>, 0 = off, for measurement)
     static const int band_env = measure_env("XCLIP_GEMM_BAND", -1);
     // FF1 forward in the step: 1227 -> 1155 us (profiles/r02_run22_gemm_banded_order.log); the widest band of 4..8 tiles that divides
@@ -952,23 +1001,10 @@ static int gemm2_run(int a_kmajor, int b_kmajor, const void* A, int64_t lda, con
     if (band_env != 0 && q.tiles_n > 8)
         for (int b = band_env > 0 ? band_env : 8; b >= 4 && q.band_n == 0; --b)
             if (q.tiles_n % b == 0) q.band_n = b;
-    int splits = gemm2_splits(M, N, K);
-    if (splits > 1 && (!plain || workspace == nullptr || workspace_bytes < (int64_t)splits * M * N * 4)) splits = 1;
-    q.k_per_split = (int)((((K / G2_BK) + splits - 1) / splits) * G2_BK);
-    // rounding the slice up can leave the last slices EMPTY (96 K steps over 17 slices -> 6 per slice, 16 slices cover them): a slice
-    // without work returns without touching its slab and the reduction would add whatever the workspace held before
-    splits = (int)((K + q.k_per_split - 1) / q.k_per_split);
-    q.partial = splits > 1 ? (float*)workspace : nullptr;
-    if (!a_kmajor && !b_kmajor) launch_gemm2<false, false>(q, splits, st);
-    else if (!a_kmajor && b_kmajor) launch_gemm2<false, true>(q, splits, st);
-    else launch_gemm2<true, true>(q, splits, st);
-    if (splits_out != nullptr) *splits_out = splits;
-    if (splits > 1 && reduce) {
-        int64_t blocks = (M * (N / 4) + 255) / 256;
-        if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL((splitk_reduce_kernel<bf16_t>), dim3((unsigned)blocks), dim3(256), 0, st, (const float*)workspace,
-                           (bf16_t*)C, (long)ldc, (int)M, (int)N, splits, alpha);
-    }
+    q.k_per_split = k_per_split;
+    q.partial = splits > 1 ? (float*)g.workspace : nullptr;
+    by_layout(g.a_kmajor, g.b_kmajor, [&](auto ak, auto bk) { launch_gemm2<decltype(ak)::value, decltype(bk)::value>(q, splits, st); });
+    if (splits > 1 && reduce) launch_splitk_reduce<bf16_t>(g.workspace, g.C, g.ldc, g.M, g.N, splits, g.alpha, nullptr, 0, st);
     return check_launch(__func__);
 }
 
@@ -979,22 +1015,20 @@ int64_t xclip_gemm_small_limit(int64_t max_flop) {
     if (max_flop >= 0) g_small_flop = max_flop;
     return was;
 }
-static int gemm_small_run(int a_kmajor, int b_kmajor, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int64_t M,
-                          int64_t N, int64_t K, float alpha, const void* residual, int64_t ldr, hipStream_t st) {
+static int gemm_small_run(const GemmArgs& g, hipStream_t st) {
     GemmSmallParams q;
-    q.A = (const bf16_t*)A; q.B = (const bf16_t*)B; q.C = (bf16_t*)C; q.lda = lda; q.ldb = ldb; q.ldc = ldc;
-    q.M = (int)M; q.N = (int)N; q.K = (int)K; q.alpha = alpha; q.residual = (const bf16_t*)residual; q.ldr = ldr;
-    q.tiles_m = (int)(M / GS_BM); q.tiles_n = (int)(N / GS_BN);
+    q.A = (const bf16_t*)g.A; q.B = (const bf16_t*)g.B; q.C = (bf16_t*)g.C; q.lda = g.lda; q.ldb = g.ldb; q.ldc = g.ldc;
+    q.M = (int)g.M; q.N = (int)g.N; q.K = (int)g.K; q.alpha = g.alpha; q.residual = (const bf16_t*)g.residual; q.ldr = g.ldr;
+    q.tiles_m = (int)(g.M / GS_BM); q.tiles_n = (int)(g.N / GS_BN);
     const int64_t tiles = (int64_t)q.tiles_m * q.tiles_n;
-    q.stages = gs_stages(tiles, K / GS_BK);
+    q.stages = gs_stages(tiles, g.K / GS_BK);
     const int lds = q.stages * GS_STAGE_BYTES;
-#define XC_GS(AK, BK_, RES) do { XC_ALLOW_LDS((gemm_small_kernel<AK, BK_, RES>), GS_MAX_STAGES * GS_STAGE_BYTES); \
+#define XC_GS(RES) do { XC_ALLOW_LDS((gemm_small_kernel<AK, BK_, RES>), GS_MAX_STAGES * GS_STAGE_BYTES); \
         hipLaunchKernelGGL((gemm_small_kernel<AK, BK_, RES>), dim3((unsigned)tiles), dim3(GS_THREADS), lds, st, q); } while (0)
-    if (residual != nullptr) {
-        if (!a_kmajor && !b_kmajor) XC_GS(false, false, true); else if (!a_kmajor) XC_GS(false, true, true); else XC_GS(true, true, true);
-    } else {
-        if (!a_kmajor && !b_kmajor) XC_GS(false, false, false); else if (!a_kmajor) XC_GS(false, true, false); else XC_GS(true, true, false);
-    }
+    by_layout(g.a_kmajor, g.b_kmajor, [&](auto ak, auto bk) {
+        constexpr bool AK = decltype(ak)::value, BK_ = decltype(bk)::value;
+        if (g.residual != nullptr) XC_GS(true); else XC_GS(false);
+    });
 #undef XC_GS
     return check_launch(__func__);
 }
@@ -1009,13 +1043,11 @@ static int gemm_small_run(int a_kmajor, int b_kmajor, const void* A, int64_t lda
 extern "C" int xclip_measure_gemm8(int on) { const int was = gemm8_on() ? 1 : 0; g_gemm8 = on; return was; }
 #endif
 
+// the plan's bytes for the most demanding caller of the shape: no terms, normal A (the only layout that cuts the row tail: a k-major-A
+// caller just gets a little more than it needs), a workspace as large as asked for, the 64 x 64 kernel turned off
 int64_t xclip_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K, int dtype) {
-    if (use_gemm2(M, N, K, dtype)) {
-        const int64_t cut = gemm2_tail_cut(M, N, K);           // (normal-A layouts only; the k-major-A caller just gets a little more than it needs)
-        if (cut > 0) return (int64_t)gemm2_splits(M - cut, N, K) * (M - cut) * N * 4;
-    }
-    const int s = use_gemm2(M, N, K, dtype) ? gemm2_splits(M, N, K) : gemm_splits(M, N, K, dtype);
-    return s > 1 ? (int64_t)s * M * N * 4 : 0;
+    GemmArgs g{}; g.M = M; g.N = N; g.K = K;
+    return gemm_plan(g, dtype, INT64_MAX, -1).workspace_bytes;
 }
 
 int xclip_gemm(int a_kmajor, int b_kmajor, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
@@ -1039,68 +1071,36 @@ int xclip_gemm(int a_kmajor, int b_kmajor, const void* A, int64_t lda, const voi
     XC_REQUIRE(addrows == nullptr || (rowidx != nullptr && ld_add % vec == 0), "addrows needs rowidx and an aligned ld");
     if (M == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    const bool plain = (bias == nullptr && residual == nullptr && addrows == nullptr);
-    if (dtype == XCLIP_BF16 && gs_takes(M, N, K, bias != nullptr || addrows != nullptr, lda, ldb, g_small_flop))
-        return gemm_small_run(a_kmajor, b_kmajor, A, lda, B, ldb, C, ldc, M, N, K, alpha, residual, ldr, st);
-    if (use_gemm2(M, N, K, dtype)) {
-        // the row tail as a split-K problem of its own (gemm2_tail_cut): the main rows, then the tail's slabs, then the reduction that also
-        // applies alpha and the skip term
-        const int64_t cut = (!a_kmajor && bias == nullptr && addrows == nullptr && workspace != nullptr) ? gemm2_tail_cut(M, N, K) : 0;
-        const int64_t mt = M - cut;
-        if (cut > 0 && gemm2_splits(mt, N, K) > 1 && workspace_bytes >= (int64_t)gemm2_splits(mt, N, K) * mt * N * 4) {
-            int rc = gemm2_run(a_kmajor, b_kmajor, A, lda, B, ldb, C, ldc, cut, N, K, alpha, nullptr, residual, ldr, nullptr, nullptr, 0, nullptr, 0, st,
-                               true, nullptr);
-            if (rc != 0) return rc;
-            const char* At = (const char*)A + cut * lda * 2;     // (bf16: use_gemm2)
-            char* Ct = (char*)C + cut * ldc * 2;
-            const char* Rt = residual != nullptr ? (const char*)residual + cut * ldr * 2 : nullptr;
-            int tsplits = 1;
-            rc = gemm2_run(a_kmajor, b_kmajor, At, lda, B, ldb, Ct, ldc, mt, N, K, alpha, nullptr, nullptr, 0, nullptr, nullptr, 0, workspace,
-                           workspace_bytes, st, false, &tsplits);
-            if (rc != 0) return rc;
-            if (tsplits > 1) {
-                int64_t blocks = (mt * (N / 4) + 255) / 256;
-                if (blocks > 4096) blocks = 4096;
-                hipLaunchKernelGGL((splitk_reduce_kernel<bf16_t>), dim3((unsigned)blocks), dim3(256), 0, st, (const float*)workspace, (bf16_t*)Ct,
-                                   (long)ldc, (int)mt, (int)N, tsplits, alpha, (const bf16_t*)Rt, (long)ldr);
-            } else if (Rt != nullptr) {
-                return xcapi::fail(__func__, "internal: tail GEMM did not split");
-            }
-            return check_launch(__func__);
-        }
-        return gemm2_run(a_kmajor, b_kmajor, A, lda, B, ldb, C, ldc, M, N, K, alpha, bias, residual, ldr, addrows, rowidx, ld_add, workspace,
-                         workspace_bytes, st, true, nullptr);
+    const GemmArgs g{a_kmajor, b_kmajor, A, lda, B, ldb, C, ldc, M, N, K, alpha, bias, residual, ldr, addrows, rowidx, ld_add, workspace, workspace_bytes};
+    const GemmPlan plan = gemm_plan(g, dtype, workspace != nullptr ? workspace_bytes : 0, g_small_flop);
+    switch (plan.route) {
+    case GEMM_SMALL: return gemm_small_run(g, st);
+    case GEMM_256: return gemm2_run(g, plan.splits, plan.k_per_split, true, st);
+    case GEMM_256_CUT: {                                      // the main rows, then the tail's slabs, then the reduction that also applies alpha and the skip term
+        GemmArgs main = g, tail = g;
+        main.M = plan.main_rows;
+        if (const int rc = gemm2_run(main, 1, (int)K, true, st)) return rc;
+        tail.M = plan.tail_rows;
+        tail.A = (const char*)A + plan.main_rows * lda * 2;   // (bf16: use_gemm2)
+        tail.C = (char*)C + plan.main_rows * ldc * 2;
+        tail.residual = nullptr; tail.ldr = 0;
+        if (const int rc = gemm2_run(tail, plan.splits, plan.k_per_split, false, st)) return rc;
+        const char* Rt = residual != nullptr ? (const char*)residual + plan.main_rows * ldr * 2 : nullptr;
+        launch_splitk_reduce<bf16_t>(workspace, tail.C, ldc, tail.M, N, plan.splits, alpha, Rt, ldr, st);
+        return check_launch(__func__);
+    }
+    case GEMM_GENERIC: break;
     }
     GemmParams p;
     p.A = A; p.B = B; p.C = C; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
     p.M = (int)M; p.N = (int)N; p.K = (int)K; p.alpha = alpha;
     p.bias = bias; p.residual = residual; p.ldr = ldr; p.addrows = addrows; p.rowidx = rowidx; p.ld_add = ld_add;
     p.tiles_m = (int)((M + 127) / 128); p.tiles_n = (int)((N + 127) / 128);
-    int splits = gemm_splits(M, N, K, dtype);
-    if (splits > 1 && (!plain || workspace == nullptr || workspace_bytes < (int64_t)splits * M * N * 4)) splits = 1;
-    const int bk = 8 * vec;
-    p.k_per_split = (int)((((K + splits - 1) / splits) + bk - 1) / bk * bk);
-    splits = (int)((K + p.k_per_split - 1) / p.k_per_split);      // no empty slices (see above)
-    p.partial = splits > 1 ? (float*)workspace : nullptr;
-    if (dtype == XCLIP_BF16) {
-        if (!a_kmajor && !b_kmajor) launch_gemm<bf16_t, false, false>(p, splits, st);
-        else if (!a_kmajor && b_kmajor) launch_gemm<bf16_t, false, true>(p, splits, st);
-        else launch_gemm<bf16_t, true, true>(p, splits, st);
-    } else {
-        if (!a_kmajor && !b_kmajor) launch_gemm<float, false, false>(p, splits, st);
-        else if (!a_kmajor && b_kmajor) launch_gemm<float, false, true>(p, splits, st);
-        else launch_gemm<float, true, true>(p, splits, st);
-    }
-    if (splits > 1) {
-        int64_t blocks = (M * (N / 4) + 255) / 256;
-        if (blocks > 4096) blocks = 4096;
-        if (dtype == XCLIP_BF16)
-            hipLaunchKernelGGL((splitk_reduce_kernel<bf16_t>), dim3((unsigned)blocks), dim3(256), 0, st, (const float*)workspace,
-                               (bf16_t*)C, (long)ldc, (int)M, (int)N, splits, alpha);
-        else
-            hipLaunchKernelGGL((splitk_reduce_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, st, (const float*)workspace,
-                               (float*)C, (long)ldc, (int)M, (int)N, splits, alpha);
-    }
+    p.k_per_split = plan.k_per_split;
+    p.partial = plan.splits > 1 ? (float*)workspace : nullptr;
+    launch_gemm(p, dtype, a_kmajor, b_kmajor, plan.splits, 1, st);
+    if (plan.splits > 1)
+        by_dtype(dtype, [&](auto t) { launch_splitk_reduce<typename decltype(t)::type>(workspace, C, ldc, M, N, plan.splits, alpha, nullptr, 0, st); });
     return check_launch(__func__);
 }
 
@@ -1113,46 +1113,48 @@ int64_t xclip_ffn_dgrad_geglu_workspace_bytes(int64_t M, int64_t F, int64_t D) {
 }
 // rowc_in != nullptr: the rows' constants are already there (written by xclip_layernorm_bwd_ffnstats in the pass that produced dout);
 // otherwise the weight vector and the row pass run here (x2 / x1 required)
-static int ffn_dgrad_geglu_run(const char* fn, const void* dout, int64_t ldd, const void* w2, int64_t ldw, const void* x, int64_t ldx, const void* gamma,
-                               const float* mean, const float* rstd, const void* x2, int64_t ld2, const void* x1, int64_t ld1, const float* rowc_in,
-                               void* dx, int64_t lddx, float* dg_accum, void* workspace, int64_t workspace_bytes, int64_t M, int64_t F, int64_t D,
-                               int dtype, void* stream) {
+struct FfnDgradArgs {                                         // xclip_ffn_dgrad_geglu's arguments, in its order, + rowc_in
+    const void* dout; int64_t ldd; const void* w2; int64_t ldw; const void* x; int64_t ldx; const void* gamma;
+    const float* mean; const float* rstd; const void* x2; int64_t ld2; const void* x1; int64_t ld1; const float* rowc_in;
+    void* dx; int64_t lddx; float* dg_accum; void* workspace; int64_t workspace_bytes; int64_t M, F, D; int dtype; void* stream;
+};
+static int ffn_dgrad_geglu_run(const char* fn, const FfnDgradArgs& a) {
 #define XC_REQ(cond, msg) do { if (!(cond)) return xcapi::fail(fn, msg); } while (0)
-    XC_REQ(xclip_ffn_dgrad_geglu_ok(M, F, D, dtype), "shape / dtype not taken by the fused kernel (xclip_ffn_dgrad_geglu_ok)");
-    XC_REQ(dout && w2 && x && gamma && dx && dg_accum, "null pointer");
-    XC_REQ(rowc_in != nullptr || (mean && rstd && x2 && x1), "null pointer");
-    XC_REQ(aligned16(dout) && aligned16(w2) && aligned16(x) && aligned16(gamma) && aligned16(x2) && aligned16(x1) && aligned16(dx) && aligned16(workspace) && aligned16(rowc_in),
+    XC_REQ(xclip_ffn_dgrad_geglu_ok(a.M, a.F, a.D, a.dtype), "shape / dtype not taken by the fused kernel (xclip_ffn_dgrad_geglu_ok)");
+    XC_REQ(a.dout && a.w2 && a.x && a.gamma && a.dx && a.dg_accum, "null pointer");
+    XC_REQ(a.rowc_in != nullptr || (a.mean && a.rstd && a.x2 && a.x1), "null pointer");
+    XC_REQ(aligned16(a.dout) && aligned16(a.w2) && aligned16(a.x) && aligned16(a.gamma) && aligned16(a.x2) && aligned16(a.x1) && aligned16(a.dx) && aligned16(a.workspace) && aligned16(a.rowc_in),
            "pointers must be 16-byte aligned");
-    XC_REQ(ldd % 8 == 0 && ldw % 8 == 0 && ldx % 8 == 0 && ld2 % 8 == 0 && ld1 % 8 == 0 && lddx % 8 == 0, "leading dimensions must be multiples of the 16-byte chunk");
-    XC_REQ(ldd >= D && (rowc_in != nullptr || (ld2 >= D && ld1 >= D)) && ldw >= F && ldx >= 2 * F && lddx >= 2 * F, "leading dimension too small");
-    XC_REQ(ldd < (1L << 22) && ldw < (1L << 22) && ldx < (1L << 22) && lddx < (1L << 22), "leading dimensions beyond the 32-bit tile offsets");
-    XC_REQ(workspace != nullptr && workspace_bytes >= xclip_ffn_dgrad_geglu_workspace_bytes(M, F, D), "workspace too small");
+    XC_REQ(a.ldd % 8 == 0 && a.ldw % 8 == 0 && a.ldx % 8 == 0 && a.ld2 % 8 == 0 && a.ld1 % 8 == 0 && a.lddx % 8 == 0, "leading dimensions must be multiples of the 16-byte chunk");
+    XC_REQ(a.ldd >= a.D && (a.rowc_in != nullptr || (a.ld2 >= a.D && a.ld1 >= a.D)) && a.ldw >= a.F && a.ldx >= 2 * a.F && a.lddx >= 2 * a.F, "leading dimension too small");
+    XC_REQ(a.ldd < (1L << 22) && a.ldw < (1L << 22) && a.ldx < (1L << 22) && a.lddx < (1L << 22), "leading dimensions beyond the 32-bit tile offsets");
+    XC_REQ(a.workspace != nullptr && a.workspace_bytes >= xclip_ffn_dgrad_geglu_workspace_bytes(a.M, a.F, a.D), "workspace too small");
 #undef XC_REQ
-    hipStream_t st = (hipStream_t)stream;
-    float* wg = (float*)workspace;
-    float* rowc = wg + (D + 3) / 4 * 4;
-    float* slab = rowc + 4 * M;
-    if (rowc_in == nullptr) {
-        hipLaunchKernelGGL(ffn_wgamma_kernel, dim3((unsigned)((D + 3) / 4)), dim3(256), 0, st, (const bf16_t*)w2, (long)ldw, (const bf16_t*)gamma, wg, (int)D, (int)F);
-        hipLaunchKernelGGL(ffn_rowstats_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, (const bf16_t*)dout, (long)ldd, (const bf16_t*)x2, (long)ld2,
-                           (const bf16_t*)x1, (long)ld1, (const float*)wg, mean, rstd, rowc, (int)M, (int)D, 1.0f / (float)F);
+    hipStream_t st = (hipStream_t)a.stream;
+    float* wg = (float*)a.workspace;
+    float* rowc = wg + (a.D + 3) / 4 * 4;
+    float* slab = rowc + 4 * a.M;
+    if (a.rowc_in == nullptr) {
+        hipLaunchKernelGGL(ffn_wgamma_kernel, dim3((unsigned)((a.D + 3) / 4)), dim3(256), 0, st, (const bf16_t*)a.w2, (long)a.ldw, (const bf16_t*)a.gamma, wg, (int)a.D, (int)a.F);
+        hipLaunchKernelGGL(ffn_rowstats_kernel, dim3((unsigned)((a.M + 3) / 4)), dim3(256), 0, st, (const bf16_t*)a.dout, (long)a.ldd, (const bf16_t*)a.x2, (long)a.ld2,
+                           (const bf16_t*)a.x1, (long)a.ld1, (const float*)wg, a.mean, a.rstd, rowc, (int)a.M, (int)a.D, 1.0f / (float)a.F);
     } else {
-        rowc = const_cast<float*>(rowc_in);
+        rowc = const_cast<float*>(a.rowc_in);
     }
     Gemm2Params q{};
-    q.A = (const bf16_t*)dout; q.B = (const bf16_t*)w2; q.C = nullptr; q.lda = ldd; q.ldb = ldw; q.ldc = F;
-    q.M = (int)M; q.N = (int)F; q.K = (int)D; q.alpha = 1.f;
+    q.A = (const bf16_t*)a.dout; q.B = (const bf16_t*)a.w2; q.C = nullptr; q.lda = a.ldd; q.ldb = a.ldw; q.ldc = a.F;
+    q.M = (int)a.M; q.N = (int)a.F; q.K = (int)a.D; q.alpha = 1.f;
     q.bias = nullptr; q.residual = nullptr; q.ldr = 0; q.addrows = nullptr; q.rowidx = nullptr; q.ld_add = 0; q.partial = nullptr;
-    q.k_per_split = (int)D;
-    q.tiles_m = (int)(M / G2_BM); q.tiles_n = (int)(F / G2_BN);
+    q.k_per_split = (int)a.D;
+    q.tiles_m = (int)(a.M / G2_BM); q.tiles_n = (int)(a.F / G2_BN);
     q.band_n = 0;
     if (q.tiles_n > 8)
         for (int b = 8; b >= 4 && q.band_n == 0; --b)
             if (q.tiles_n % b == 0) q.band_n = b;
     q.stream_out = 1;
     GegluBwdArgs e;
-    e.x = (const bf16_t*)x; e.ldx = ldx; e.dx = (bf16_t*)dx; e.lddx = lddx; e.gamma = (const bf16_t*)gamma;
-    e.rowc = rowc; e.dg_partial = slab; e.F = (int)F;
+    e.x = (const bf16_t*)a.x; e.ldx = a.ldx; e.dx = (bf16_t*)a.dx; e.lddx = a.lddx; e.gamma = (const bf16_t*)a.gamma;
+    e.rowc = rowc; e.dg_partial = slab; e.F = (int)a.F;
 
     int gx = q.tiles_m * q.tiles_n;
     const int cus = xc_num_cus();
@@ -1180,8 +1182,8 @@ static int ffn_dgrad_geglu_run(const char* fn, const void* dout, int64_t ldd, co
     const int nrows = 2 * q.tiles_m;
     int slices = nrows / 64;
     if (slices < 1) slices = 1;
-    hipLaunchKernelGGL(colsum_fold_kernel, dim3((unsigned)((F + 63) / 64), (unsigned)slices), dim3(256), 1024, st, (const float*)slab, (long)F, dg_accum,
-                       nrows, (int)F);
+    hipLaunchKernelGGL(colsum_fold_kernel, dim3((unsigned)((a.F + 63) / 64), (unsigned)slices), dim3(256), 1024, st, (const float*)slab, (long)a.F, a.dg_accum,
+                       nrows, (int)a.F);
     return check_launch(fn);
 }
 int xclip_ffn_dgrad_geglu(const void* dout, int64_t ldd, const void* w2, int64_t ldw, const void* x, int64_t ldx, const void* gamma,
@@ -1189,15 +1191,15 @@ int xclip_ffn_dgrad_geglu(const void* dout, int64_t ldd, const void* w2, int64_t
                           int64_t lddx, float* dg_accum, void* workspace, int64_t workspace_bytes, int64_t M, int64_t F, int64_t D,
                           int dtype, void* stream) {
     XC_REQUIRE(mean && rstd && x2 && x1, "null pointer");
-    return ffn_dgrad_geglu_run(__func__, dout, ldd, w2, ldw, x, ldx, gamma, mean, rstd, x2, ld2, x1, ld1, nullptr, dx, lddx, dg_accum, workspace,
-                               workspace_bytes, M, F, D, dtype, stream);
+    return ffn_dgrad_geglu_run(__func__, {dout, ldd, w2, ldw, x, ldx, gamma, mean, rstd, x2, ld2, x1, ld1, nullptr, dx, lddx, dg_accum, workspace,
+                                          workspace_bytes, M, F, D, dtype, stream});
 }
 int xclip_ffn_dgrad_geglu_rowc(const void* dout, int64_t ldd, const void* w2, int64_t ldw, const void* x, int64_t ldx, const void* gamma,
                                const float* rowc, void* dx, int64_t lddx, float* dg_accum, void* workspace, int64_t workspace_bytes,
                                int64_t M, int64_t F, int64_t D, int dtype, void* stream) {
     XC_REQUIRE(rowc != nullptr, "null pointer");
-    return ffn_dgrad_geglu_run(__func__, dout, ldd, w2, ldw, x, ldx, gamma, nullptr, nullptr, nullptr, 0, nullptr, 0, rowc, dx, lddx, dg_accum, workspace,
-                               workspace_bytes, M, F, D, dtype, stream);
+    return ffn_dgrad_geglu_run(__func__, {dout, ldd, w2, ldw, x, ldx, gamma, nullptr, nullptr, nullptr, 0, nullptr, 0, rowc, dx, lddx, dg_accum, workspace,
+                                          workspace_bytes, M, F, D, dtype, stream});
 }
 int xclip_ffn_wgamma(const void* w2, int64_t ldw, const void* gamma, float* wg, int64_t D, int64_t F, int dtype, void* stream) {
     XC_REQUIRE(dtype == XCLIP_BF16, "bf16 only (the fused feed-forward backward)");
@@ -1228,15 +1230,7 @@ int xclip_gemm_batched(int a_kmajor, int b_kmajor, const void* A, int64_t lda, i
     p.tiles_m = (int)((M + 127) / 128); p.tiles_n = (int)((N + 127) / 128);
     p.k_per_split = (int)((K + 8 * vec - 1) / (8 * vec) * (8 * vec));
     p.batch_a = stride_a; p.batch_b = stride_b; p.batch_c = stride_c;
-    dim3 grid(p.tiles_m * p.tiles_n, 1, (unsigned)batch), block(GEMM_THREADS);
-    hipStream_t st = (hipStream_t)stream;
-#define XC_GB(T, AK, BK_) do { XC_ALLOW_LDS((gemm_kernel<T, AK, BK_>), GemmCfg<T>::LDS_BYTES); hipLaunchKernelGGL((gemm_kernel<T, AK, BK_>), grid, block, GemmCfg<T>::LDS_BYTES, st, p); } while (0)
-    if (dtype == XCLIP_BF16) {
-        if (!a_kmajor && !b_kmajor) XC_GB(bf16_t, false, false); else if (!a_kmajor) XC_GB(bf16_t, false, true); else XC_GB(bf16_t, true, true);
-    } else {
-        if (!a_kmajor && !b_kmajor) XC_GB(float, false, false); else if (!a_kmajor) XC_GB(float, false, true); else XC_GB(float, true, true);
-    }
-#undef XC_GB
+    launch_gemm(p, dtype, a_kmajor, b_kmajor, 1, batch, (hipStream_t)stream);
     return check_launch(__func__);
 }
 
@@ -1275,20 +1269,17 @@ int xclip_filip_reduce(const void* S, int64_t lds, const uint8_t* mask, const fl
         nsplit = (yc + ysplit - 1) / ysplit;
         const int64_t nchunks = (ysplit * ni + vec - 1) / vec;
         const size_t shm = (size_t)nchunks * 32 + (size_t)ysplit * 4;
-        XC_ALLOW_LDS((filip_reduce_rows_kernel<bf16_t>), 96 * 1024);
-        XC_ALLOW_LDS((filip_reduce_rows_kernel<float>), 96 * 1024);
         dim3 g2((unsigned)bx, (unsigned)nsplit), b2(256);
-        if (dtype == XCLIP_BF16)
-            hipLaunchKernelGGL((filip_reduce_rows_kernel<bf16_t>), g2, b2, shm, (hipStream_t)stream, (const bf16_t*)S, (long)lds, mask, log_temp, t2i, i2t, (long)ldo, kmax, tmax, cnt, (int)bx, (int)nt, (int)yc, (int)ni, (int)y0, (int)ytotal, (int)ysplit);
-        else
-            hipLaunchKernelGGL((filip_reduce_rows_kernel<float>), g2, b2, shm, (hipStream_t)stream, (const float*)S, (long)lds, mask, log_temp, t2i, i2t, (long)ldo, kmax, tmax, cnt, (int)bx, (int)nt, (int)yc, (int)ni, (int)y0, (int)ytotal, (int)ysplit);
+        by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+            XC_ALLOW_LDS((filip_reduce_rows_kernel<T>), 96 * 1024);
+            hipLaunchKernelGGL((filip_reduce_rows_kernel<T>), g2, b2, shm, (hipStream_t)stream, (const T*)S, (long)lds, mask, log_temp, t2i, i2t, (long)ldo, kmax, tmax, cnt, (int)bx, (int)nt, (int)yc, (int)ni, (int)y0, (int)ytotal, (int)ysplit);
+        });
         return check_launch(__func__);
     }
     dim3 grid((unsigned)((bx * yc + 3) / 4)), block(256);
-    if (dtype == XCLIP_BF16)
-        hipLaunchKernelGGL((filip_reduce_kernel<bf16_t>), grid, block, 0, (hipStream_t)stream, (const bf16_t*)S, (long)lds, mask, log_temp, t2i, i2t, (long)ldo, kmax, tmax, cnt, (int)bx, (int)nt, (int)yc, (int)ni, (int)y0, (int)ytotal);
-    else
-        hipLaunchKernelGGL((filip_reduce_kernel<float>), grid, block, 0, (hipStream_t)stream, (const float*)S, (long)lds, mask, log_temp, t2i, i2t, (long)ldo, kmax, tmax, cnt, (int)bx, (int)nt, (int)yc, (int)ni, (int)y0, (int)ytotal);
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((filip_reduce_kernel<T>), grid, block, 0, (hipStream_t)stream, (const T*)S, (long)lds, mask, log_temp, t2i, i2t, (long)ldo, kmax, tmax, cnt, (int)bx, (int)nt, (int)yc, (int)ni, (int)y0, (int)ytotal);
+    });
     return check_launch(__func__);
 }
 
@@ -1337,13 +1328,10 @@ int xclip_filip_route(void* P, int64_t ldp, int64_t pcols, const uint8_t* mask, 
     XC_REQUIRE(bx * nt < (1LL << 31) && pcols / vec_of(dtype) < (1LL << 31) && bx <= 65535, "chunk too large for the launch grid");
     // one work-group per (text x, slice of 256 chunks): blockIdx.y = x
     dim3 grid((unsigned)((pcols / vec_of(dtype) + 255) / 256), (unsigned)bx), block(256);
-    if (dtype == XCLIP_BF16) {
-        XC_ALLOW_LDS((filip_route_kernel<bf16_t>), ROUTE_LDS_BYTES);
-        hipLaunchKernelGGL((filip_route_kernel<bf16_t>), grid, block, ROUTE_LDS_BYTES, (hipStream_t)stream, (bf16_t*)P, (long)ldp, (long)pcols, mask, log_temp, g1, g2, (long)ldg, kmax, tmax, cnt, (int)bx, (int)nt, (int)yc, (int)ni, (int)y0, (int)ytotal);
-    } else {
-        XC_ALLOW_LDS((filip_route_kernel<float>), ROUTE_LDS_BYTES);
-        hipLaunchKernelGGL((filip_route_kernel<float>), grid, block, ROUTE_LDS_BYTES, (hipStream_t)stream, (float*)P, (long)ldp, (long)pcols, mask, log_temp, g1, g2, (long)ldg, kmax, tmax, cnt, (int)bx, (int)nt, (int)yc, (int)ni, (int)y0, (int)ytotal);
-    }
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        XC_ALLOW_LDS((filip_route_kernel<T>), ROUTE_LDS_BYTES);
+        hipLaunchKernelGGL((filip_route_kernel<T>), grid, block, ROUTE_LDS_BYTES, (hipStream_t)stream, (T*)P, (long)ldp, (long)pcols, mask, log_temp, g1, g2, (long)ldg, kmax, tmax, cnt, (int)bx, (int)nt, (int)yc, (int)ni, (int)y0, (int)ytotal);
+    });
     return check_launch(__func__);
 }
 
@@ -1497,10 +1485,9 @@ int xclip_simrank_pos(const void* Q, const void* K, int64_t nq, int64_t nk, int6
     XC_REQUIRE(thr != nullptr, "thr required");
     dim3 grid((unsigned)((nq + 3) / 4)), block(256);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == XCLIP_BF16)
-        hipLaunchKernelGGL((simrank_pos_kernel<bf16_t>), grid, block, 0, st, (const bf16_t*)Q, (const bf16_t*)K, (int)nq, (int)nk, (int)d, scale, log_scale, (int)diag_off, thr);
-    else
-        hipLaunchKernelGGL((simrank_pos_kernel<float>), grid, block, 0, st, (const float*)Q, (const float*)K, (int)nq, (int)nk, (int)d, scale, log_scale, (int)diag_off, thr);
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((simrank_pos_kernel<T>), grid, block, 0, st, (const T*)Q, (const T*)K, (int)nq, (int)nk, (int)d, scale, log_scale, (int)diag_off, thr);
+    });
     return check_launch(__func__);
 }
 
@@ -1631,12 +1618,9 @@ int xclip_simreg_diff(const void* A, int64_t lda, const void* C, int64_t ldc, vo
     int64_t blocks = (rows + 3) / 4;
     if (blocks > 4096) blocks = 4096;
     dim3 grid((unsigned)blocks), block(256);
-    if (dtype == XCLIP_BF16)
-        hipLaunchKernelGGL((simreg_diff_kernel<bf16_t>), grid, block, 16, (hipStream_t)stream, (const bf16_t*)A, (long)lda, (const bf16_t*)C,
-                           (long)ldc, (bf16_t*)D, (long)ldd, (int)rows, (int)cols, (int)diag_off, sumsq_accum);
-    else
-        hipLaunchKernelGGL((simreg_diff_kernel<float>), grid, block, 16, (hipStream_t)stream, (const float*)A, (long)lda, (const float*)C,
-                           (long)ldc, (float*)D, (long)ldd, (int)rows, (int)cols, (int)diag_off, sumsq_accum);
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((simreg_diff_kernel<T>), grid, block, 16, (hipStream_t)stream, (const T*)A, (long)lda, (const T*)C, (long)ldc, (T*)D, (long)ldd, (int)rows, (int)cols, (int)diag_off, sumsq_accum);
+    });
     return check_launch(__func__);
 }
 
@@ -1682,21 +1666,18 @@ int xclip_batchnorm_fwd(const void* x, const float* gamma, const float* beta, vo
     float* part = (float*)workspace;
     if (training) {
         const int lds = 256 * 2 * vec_of(dtype) * (int)sizeof(float);
-        if (dtype == XCLIP_BF16) {
-            hipLaunchKernelGGL((bn_stats_kernel<bf16_t>), grid, block, lds, st, (const bf16_t*)x, part, R, C, g.cw);
-            hipLaunchKernelGGL((bn_finalize_kernel<bf16_t>), dim3(fin_blocks), block, 2048, st, (const bf16_t*)x, part, g.slices, R, C, eps, momentum,
+        by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+            hipLaunchKernelGGL((bn_stats_kernel<T>), grid, block, lds, st, (const T*)x, part, R, C, g.cw);
+            hipLaunchKernelGGL((bn_finalize_kernel<T>), dim3(fin_blocks), block, 2048, st, (const T*)x, part, g.slices, R, C, eps, momentum,
                                mean, rstd, running_mean, running_var);
-        } else {
-            hipLaunchKernelGGL((bn_stats_kernel<float>), grid, block, lds, st, (const float*)x, part, R, C, g.cw);
-            hipLaunchKernelGGL((bn_finalize_kernel<float>), dim3(fin_blocks), block, 2048, st, (const float*)x, part, g.slices, R, C, eps, momentum,
-                               mean, rstd, running_mean, running_var);
-        }
+        });
     } else {
         hipLaunchKernelGGL(bn_eval_stats_kernel, dim3(fin_blocks), block, 0, st, running_mean, running_var, eps, mean, rstd, C);
     }
-#define BN_APPLY(T, RELU) hipLaunchKernelGGL((bn_apply_kernel<T, RELU>), grid, block, 0, st, (const T*)x, mean, rstd, gamma, beta, (T*)y, R, C, g.cw)
-    if (dtype == XCLIP_BF16) { if (relu) BN_APPLY(bf16_t, true); else BN_APPLY(bf16_t, false); }
-    else                     { if (relu) BN_APPLY(float, true); else BN_APPLY(float, false); }
+#define BN_APPLY(RELU) hipLaunchKernelGGL((bn_apply_kernel<T, RELU>), grid, block, 0, st, (const T*)x, mean, rstd, gamma, beta, (T*)y, R, C, g.cw)
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        if (relu) BN_APPLY(true); else BN_APPLY(false);
+    });
 #undef BN_APPLY
     return check_launch(__func__);
 }
@@ -1716,14 +1697,15 @@ int xclip_batchnorm_bwd(const void* x, const void* dy, const float* gamma, const
     float* coef = part + (int64_t)2 * BN_MAX_SLICES * cols;
     const BnCols cols_p{mean, rstd, gamma, beta};
     const int lds = 256 * 2 * vec_of(dtype) * (int)sizeof(float);
-#define BN_BWD(T, RELU)                                                                                                              \
+#define BN_BWD(RELU)                                                                                                                 \
     do {                                                                                                                             \
         hipLaunchKernelGGL((bn_bwd_sums_kernel<T, RELU>), grid, block, lds, st, (const T*)x, (const T*)dy, cols_p, part, R, C, g.cw); \
         hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 63) / 64), block, 2048, st, part, g.slices, R, C, training, dgamma, dbeta, coef); \
         hipLaunchKernelGGL((bn_bwd_apply_kernel<T, RELU>), grid, block, 0, st, (const T*)x, (const T*)dy, cols_p, coef, (T*)dx, R, C, g.cw); \
     } while (0)
-    if (dtype == XCLIP_BF16) { if (relu) BN_BWD(bf16_t, true); else BN_BWD(bf16_t, false); }
-    else                     { if (relu) BN_BWD(float, true); else BN_BWD(float, false); }
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        if (relu) BN_BWD(true); else BN_BWD(false);
+    });
 #undef BN_BWD
     return check_launch(__func__);
 }
@@ -1737,10 +1719,9 @@ int xclip_neg_cosine_fwd(const void* p, const void* z, int64_t rows, int64_t dim
     int64_t blocks = (rows + 3) / 4;
     if (blocks > ROWLOSS_MAX_BLOCKS) blocks = ROWLOSS_MAX_BLOCKS;
     dim3 grid((unsigned)blocks), block(256);
-    if (dtype == XCLIP_BF16)
-        hipLaunchKernelGGL((neg_cosine_fwd_kernel<bf16_t>), grid, block, 16, (hipStream_t)stream, (const bf16_t*)p, (const bf16_t*)z, (int)rows, (int)dim, coef, cosv, rp, rz, loss_accum);
-    else
-        hipLaunchKernelGGL((neg_cosine_fwd_kernel<float>), grid, block, 16, (hipStream_t)stream, (const float*)p, (const float*)z, (int)rows, (int)dim, coef, cosv, rp, rz, loss_accum);
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((neg_cosine_fwd_kernel<T>), grid, block, 16, (hipStream_t)stream, (const T*)p, (const T*)z, (int)rows, (int)dim, coef, cosv, rp, rz, loss_accum);
+    });
     return check_launch(__func__);
 }
 
@@ -1751,10 +1732,9 @@ int xclip_neg_cosine_bwd(const void* p, const void* z, const float* cosv, const 
     if (rows == 0) return 0;                                  // (an empty tensor has a null data pointer)
     XC_REQUIRE(p && z && cosv && rp && rz && gmul && dp && aligned16(p) && aligned16(z) && aligned16(dp), "null or misaligned pointer");
     dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-    if (dtype == XCLIP_BF16)
-        hipLaunchKernelGGL((neg_cosine_bwd_kernel<bf16_t>), grid, block, 0, (hipStream_t)stream, (const bf16_t*)p, (const bf16_t*)z, cosv, rp, rz, gmul, coef, (bf16_t*)dp, (int)rows, (int)dim);
-    else
-        hipLaunchKernelGGL((neg_cosine_bwd_kernel<float>), grid, block, 0, (hipStream_t)stream, (const float*)p, (const float*)z, cosv, rp, rz, gmul, coef, (float*)dp, (int)rows, (int)dim);
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((neg_cosine_bwd_kernel<T>), grid, block, 0, (hipStream_t)stream, (const T*)p, (const T*)z, cosv, rp, rz, gmul, coef, (T*)dp, (int)rows, (int)dim);
+    });
     return check_launch(__func__);
 }
 
@@ -1765,10 +1745,9 @@ int xclip_gradnorm_partial(const void* table, int64_t chunk0, int64_t count, int
     if (count == 0) return 0;
     XC_REQUIRE(table && partials && aligned16(table), "null or misaligned pointer");
     dim3 grid((unsigned)count), block(OPT_THREADS);
-    if (g_dtype == XCLIP_BF16)
-        hipLaunchKernelGGL((gradnorm_partial_kernel<bf16_t>), grid, block, 16, (hipStream_t)stream, (const OptChunk*)table, (int)chunk0, partials);
-    else
-        hipLaunchKernelGGL((gradnorm_partial_kernel<float>), grid, block, 16, (hipStream_t)stream, (const OptChunk*)table, (int)chunk0, partials);
+    by_dtype(g_dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((gradnorm_partial_kernel<T>), grid, block, 16, (hipStream_t)stream, (const OptChunk*)table, (int)chunk0, partials);
+    });
     return check_launch(__func__);
 }
 

@@ -59,6 +59,56 @@ int attn_waves(int64_t n) {
     return best;
 }
 
+// the run-time wave count / causal flag as template arguments (api_common.h by_dtype)
+template <typename F> inline void by_waves(int nw, F&& f) {
+    switch (nw) { case 1: f(int_tag<1>{}); break; case 2: f(int_tag<2>{}); break; case 3: f(int_tag<3>{}); break; default: f(int_tag<4>{}); break; }
+}
+template <typename F> inline void by_causal(int causal, F&& f) {
+    if (causal) f(bool_tag<true>{}); else f(bool_tag<false>{});
+}
+
+// ---- what xclip_attention_fwd and xclip_attention_bwd share ----
+enum AttnRoute {
+    ATTN_WIDE_RESIDENT,      // wide heads, head-resident (attention4.h)
+    ATTN_WIDE_TILED,         // wide heads, long sequences / fp32 / dropout: the tiled kernels with two 64-wide halves per head
+    ATTN_RESIDENT,           // head-resident kernels: one work-group per (batch, head) (attention3.h, attention5.h)
+    ATTN_TILED_BF16,         // long bf16 sequences (attention2.h)
+    ATTN_TILED,              // fp32, and bf16 with dropout (attention.h)
+};
+// tiled_only: dropout lives in the tiled kernels (attention.h)
+inline AttnRoute attn_route(int64_t head_dim, int dtype, int64_t n, bool tiled_only) {
+    const bool resident = dtype == XCLIP_BF16 && n <= A3_MAX_N && !tiled_only;
+    if (head_dim == 128) return resident ? ATTN_WIDE_RESIDENT : ATTN_WIDE_TILED;
+    if (resident) return ATTN_RESIDENT;
+    return dtype == XCLIP_BF16 && !tiled_only ? ATTN_TILED_BF16 : ATTN_TILED;
+}
+
+struct AttnCall {                                             // the arguments both take
+    const void* qkv; const uint8_t* mask; int64_t batch, n, heads, head_dim;
+    float scale; int causal; float dropout_p; uint64_t dropout_seed; int dtype;
+};
+// the common checks (ptrs_aligned: the entry point's own pointers) and the common fields of AttnParams; -> 0, or 1 with the error recorded
+// under the entry point's name `fn`.  An empty batch (the caller returns 0) stops before the dropout check, as it always has.
+int attn_setup(const char* fn, const AttnCall& c, bool ptrs_aligned, AttnParams& p, AttnRoute& route) {
+#define XC_REQ(cond, msg) do { if (!(cond)) return xcapi::fail(fn, msg); } while (0)
+    XC_REQ(dtype_ok(c.dtype), "bad dtype");
+    XC_REQ(c.batch >= 0 && c.n > 0 && c.heads > 0, "bad shape");
+    XC_REQ(c.head_dim == 64 || c.head_dim == 128, "head_dim must be 64 or 128 (narrower / in-between widths are zero-padded by the caller)");
+    XC_REQ(ptrs_aligned, "pointers must be 16-byte aligned");
+    if (c.batch == 0) return 0;
+    memset(&p, 0, sizeof(p));
+    p.qkv = c.qkv; p.mask = c.mask;
+    p.batch = (int)c.batch; p.n = (int)c.n; p.heads = (int)c.heads; p.scale = c.scale; p.causal = c.causal != 0;
+    p.first_round = 2 * xc_num_cus();
+    XC_REQ(c.dropout_p >= 0.f && c.dropout_p < 1.f, "dropout_p must lie in [0, 1)");
+    p.drop_thresh = drop_thresh(c.dropout_p); p.drop_scale = 1.0f / (1.0f - c.dropout_p); p.drop_seed = c.dropout_seed;
+    route = attn_route(c.head_dim, c.dtype, c.n, p.drop_thresh != 0);
+    XC_REQ((route != ATTN_WIDE_RESIDENT && route != ATTN_RESIDENT) || c.scale > 0.f,
+           "the head-resident kernels take the score maximum before scaling: scale must be positive");
+    return 0;
+#undef XC_REQ
+}
+
 // ---- one query row per (sample, head): the last layer of a tower whose caller reads a single token row (kernels/attention_pool.h) ----
 template <typename T>
 int launch_attn_pool(const AttnPoolParams& p, int64_t head_dim, bool backward, hipStream_t st) {
@@ -78,43 +128,28 @@ extern "C" {
 
 int xclip_attention_fwd(const void* qkv, const uint8_t* mask, void* out, float* lse, int64_t batch, int64_t n, int64_t heads,
                         int64_t head_dim, float scale, int causal, float dropout_p, uint64_t dropout_seed, int dtype, void* stream) {
-    XC_REQUIRE(dtype_ok(dtype), "bad dtype");
-    XC_REQUIRE(batch >= 0 && n > 0 && heads > 0, "bad shape");
-    XC_REQUIRE(head_dim == 64 || head_dim == 128, "head_dim must be 64 or 128 (narrower / in-between widths are zero-padded by the caller)");
-    XC_REQUIRE(aligned16(qkv) && aligned16(out), "pointers must be 16-byte aligned");
-    if (batch == 0) return 0;
-    AttnParams p;
-    memset(&p, 0, sizeof(p));
-    p.qkv = qkv; p.mask = mask; p.out = out; p.lse = lse;
-    p.batch = (int)batch; p.n = (int)n; p.heads = (int)heads; p.scale = scale; p.causal = causal != 0;
-    p.first_round = 2 * xc_num_cus();
-    XC_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "dropout_p must lie in [0, 1)");
-    p.drop_thresh = drop_thresh(dropout_p); p.drop_scale = 1.0f / (1.0f - dropout_p); p.drop_seed = dropout_seed;
-    const bool tiled_only = p.drop_thresh != 0;               // dropout lives in the tiled kernels (attention.h)
+    const AttnCall call{qkv, mask, batch, n, heads, head_dim, scale, causal, dropout_p, dropout_seed, dtype};
+    AttnParams p; AttnRoute route;
+    const int rc = attn_setup(__func__, call, aligned16(qkv) && aligned16(out), p, route);
+    if (rc != 0 || batch == 0) return rc;
+    p.out = out; p.lse = lse;
     hipStream_t st = (hipStream_t)stream;
-    if (head_dim == 128 && dtype == XCLIP_BF16 && n <= A3_MAX_N && !tiled_only) {   // wide heads, head-resident (attention4.h)
-        XC_REQUIRE(scale > 0.f, "the head-resident kernels take the score maximum before scaling: scale must be positive");
+    const dim3 hgrid((unsigned)(batch * heads));             // the head-resident kernels: one work-group per (batch, head)
+    const int nw = attn_waves(n);                             // the tiled ones
+    switch (route) {
+    case ATTN_WIDE_RESIDENT: {
         const int nwq = a4_fwd_waves((int)n);
         XC_REQUIRE(attn4_fwd_lds_bytes((int)n) <= 160 * 1024, "internal: wide-head forward LDS");
-        if (causal) {
-            XC_ALLOW_LDS(attn4_fwd_kernel<true>, 160 * 1024);
-            hipLaunchKernelGGL(attn4_fwd_kernel<true>, dim3((unsigned)(batch * heads)), dim3(nwq * 64), attn4_fwd_lds_bytes((int)n), st, p);
-        } else {
-            XC_ALLOW_LDS(attn4_fwd_kernel<false>, 160 * 1024);
-            hipLaunchKernelGGL(attn4_fwd_kernel<false>, dim3((unsigned)(batch * heads)), dim3(nwq * 64), attn4_fwd_lds_bytes((int)n), st, p);
-        }
-        return check_launch(__func__);
+        by_causal(causal, [&](auto c) {
+            XC_ALLOW_LDS(attn4_fwd_kernel<decltype(c)::value>, 160 * 1024);
+            hipLaunchKernelGGL(attn4_fwd_kernel<decltype(c)::value>, hgrid, dim3(nwq * 64), attn4_fwd_lds_bytes((int)n), st, p);
+        });
+        break;
     }
-    if (head_dim == 128) {                                     // wide heads, long sequences / fp32 / dropout: the tiled kernels with two 64-wide halves per head
-        const int nw = attn_waves(n);
-#define W(T) switch (nw) { case 1: launch_attn_fwd<T, 1, 2>(p, st); break; case 2: launch_attn_fwd<T, 2, 2>(p, st); break; \
-                           case 3: launch_attn_fwd<T, 3, 2>(p, st); break; default: launch_attn_fwd<T, 4, 2>(p, st); break; }
-        if (dtype == XCLIP_BF16) { W(bf16_t) } else { W(float) }
-#undef W
-        return check_launch(__func__);
-    }
-    if (dtype == XCLIP_BF16 && n <= A3_MAX_N && !tiled_only) {               // head-resident kernel: one work-group per (batch, head)
-        XC_REQUIRE(scale > 0.f, "the head-resident kernels take the score maximum before scaling: scale must be positive");
+    case ATTN_WIDE_TILED:
+        by_dtype(dtype, [&](auto t) { by_waves(nw, [&](auto w) { launch_attn_fwd<typename decltype(t)::type, decltype(w)::value, 2>(p, st); }); });
+        break;
+    case ATTN_RESIDENT: {
         const int nwq = a3_waves((int)n);
         // half a head's time (13 us at n = 257, growing with n^2) between the two work-groups of a CU: 0.413 -> 0.376 ms at
         // b = 1024, n = 257 (profiles/r02_run20_attention_stagger_sweep.log); XCLIP_ATTN_STAGGER_FWD=<10 ns ticks> overrides
@@ -123,73 +158,52 @@ int xclip_attention_fwd(const void* qkv, const uint8_t* mask, void* out, float* 
         p.stagger_10ns = (attn3_fwd_lds_bytes((int)n) <= 80 * 1024 && batch * heads >= 1024) ? (stag >= 0 ? stag : half_head) : 0;
         static const int abl_f = measure_env("XCLIP_ATTN_ABL", 0);  // measurement build only: 4 = the tail row as a 33rd block (round-3 form)
         p.chunks = abl_f;
-        if (causal) {
-            XC_ALLOW_LDS(attn3_fwd_kernel<true>, 160 * 1024);
-            hipLaunchKernelGGL(attn3_fwd_kernel<true>, dim3((unsigned)(batch * heads)), dim3(nwq * 64), attn3_fwd_lds_bytes((int)n), st, p);
-        } else {
-            XC_ALLOW_LDS(attn3_fwd_kernel<false>, 160 * 1024);
-            hipLaunchKernelGGL(attn3_fwd_kernel<false>, dim3((unsigned)(batch * heads)), dim3(nwq * 64), attn3_fwd_lds_bytes((int)n), st, p);
-        }
-        return check_launch(__func__);
+        by_causal(causal, [&](auto c) {
+            XC_ALLOW_LDS(attn3_fwd_kernel<decltype(c)::value>, 160 * 1024);
+            hipLaunchKernelGGL(attn3_fwd_kernel<decltype(c)::value>, hgrid, dim3(nwq * 64), attn3_fwd_lds_bytes((int)n), st, p);
+        });
+        break;
     }
-    const int nw = attn_waves(n);
-#define F(T) switch (nw) { case 1: launch_attn_fwd<T, 1>(p, st); break; case 2: launch_attn_fwd<T, 2>(p, st); break; \
-                           case 3: launch_attn_fwd<T, 3>(p, st); break; default: launch_attn_fwd<T, 4>(p, st); break; }
-    if (dtype == XCLIP_BF16 && tiled_only) { F(bf16_t) }
-    else if (dtype == XCLIP_BF16) {
-        switch (nw) { case 1: launch_attn2_fwd<1>(p, st); break; case 2: launch_attn2_fwd<2>(p, st); break;
-                      case 3: launch_attn2_fwd<3>(p, st); break; default: launch_attn2_fwd<4>(p, st); break; }
-    } else { F(float) }
-#undef F
+    case ATTN_TILED_BF16:
+        by_waves(nw, [&](auto w) { launch_attn2_fwd<decltype(w)::value>(p, st); });
+        break;
+    case ATTN_TILED:
+        by_dtype(dtype, [&](auto t) { by_waves(nw, [&](auto w) { launch_attn_fwd<typename decltype(t)::type, decltype(w)::value>(p, st); }); });
+        break;
+    }
     return check_launch(__func__);
 }
 
 int xclip_attention_bwd(const void* qkv, const uint8_t* mask, const void* out, const void* dout, const float* lse,
                         float* delta_ws, void* dqkv, int64_t batch, int64_t n, int64_t heads, int64_t head_dim, float scale, int causal,
                         float dropout_p, uint64_t dropout_seed, int dtype, void* stream) {
-    XC_REQUIRE(dtype_ok(dtype), "bad dtype");
-    XC_REQUIRE(batch >= 0 && n > 0 && heads > 0, "bad shape");
-    XC_REQUIRE(head_dim == 64 || head_dim == 128, "head_dim must be 64 or 128 (narrower / in-between widths are zero-padded by the caller)");
-    XC_REQUIRE(aligned16(qkv) && aligned16(out) && aligned16(dout) && aligned16(dqkv), "pointers must be 16-byte aligned");
-    if (batch == 0) return 0;
-    AttnParams p;
-    memset(&p, 0, sizeof(p));
-    p.qkv = qkv; p.mask = mask; p.out = const_cast<void*>(out); p.lse = const_cast<float*>(lse); p.dout = dout;
-    p.delta = delta_ws; p.dqkv = dqkv;
-    p.batch = (int)batch; p.n = (int)n; p.heads = (int)heads; p.scale = scale; p.causal = causal != 0;
-    p.first_round = 2 * xc_num_cus();
-    XC_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "dropout_p must lie in [0, 1)");
-    p.drop_thresh = drop_thresh(dropout_p); p.drop_scale = 1.0f / (1.0f - dropout_p); p.drop_seed = dropout_seed;
-    const bool tiled_only = p.drop_thresh != 0;               // dropout lives in the tiled kernels (attention.h)
+    const AttnCall call{qkv, mask, batch, n, heads, head_dim, scale, causal, dropout_p, dropout_seed, dtype};
+    AttnParams p; AttnRoute route;
+    const int rc = attn_setup(__func__, call, aligned16(qkv) && aligned16(out) && aligned16(dout) && aligned16(dqkv), p, route);
+    if (rc != 0 || batch == 0) return rc;
+    p.out = const_cast<void*>(out); p.lse = const_cast<float*>(lse); p.dout = dout; p.delta = delta_ws; p.dqkv = dqkv;
     hipStream_t st = (hipStream_t)stream;
-    if (head_dim == 128 && dtype == XCLIP_BF16 && n <= A3_MAX_N && !tiled_only) {   // wide heads, head-resident (attention4.h; computes delta itself)
-        XC_REQUIRE(scale > 0.f, "the head-resident kernels take the score maximum before scaling: scale must be positive");
+    const dim3 hgrid((unsigned)(batch * heads));             // the head-resident kernels: one work-group per (batch, head)
+    const dim3 dgrid((unsigned)((batch * n + 3) / 4)), dblock(256);   // the tiled ones' delta pass
+    const int nw = attn_waves(n);
+    switch (route) {
+    case ATTN_WIDE_RESIDENT: {                                 // (computes delta itself)
         const int nwq = a3_bwd_waves((int)n);
-        if (causal) {
-            XC_ALLOW_LDS(attn4_bwd_kernel<true>, 160 * 1024);
-            hipLaunchKernelGGL(attn4_bwd_kernel<true>, dim3((unsigned)(batch * heads)), dim3(nwq * 64), attn4_bwd_lds_bytes((int)n), st, p);
-        } else {
-            XC_ALLOW_LDS(attn4_bwd_kernel<false>, 160 * 1024);
-            hipLaunchKernelGGL(attn4_bwd_kernel<false>, dim3((unsigned)(batch * heads)), dim3(nwq * 64), attn4_bwd_lds_bytes((int)n), st, p);
-        }
-        return check_launch(__func__);
+        by_causal(causal, [&](auto c) {
+            XC_ALLOW_LDS(attn4_bwd_kernel<decltype(c)::value>, 160 * 1024);
+            hipLaunchKernelGGL(attn4_bwd_kernel<decltype(c)::value>, hgrid, dim3(nwq * 64), attn4_bwd_lds_bytes((int)n), st, p);
+        });
+        break;
     }
-    if (head_dim == 128) {                                     // wide heads, long sequences / fp32 / dropout: delta pass + the tiled dQ / dK, dV kernels on two halves
+    case ATTN_WIDE_TILED:                                      // delta pass + the tiled dQ / dK, dV kernels on two halves
         XC_REQUIRE(delta_ws != nullptr, "wide heads need the [batch, heads, n] fp32 delta workspace");
-        dim3 wgrid((unsigned)((batch * n + 3) / 4)), wblock(256);
         if (dtype == XCLIP_BF16)
-            hipLaunchKernelGGL((attn_delta_kernel<bf16_t, 2>), wgrid, wblock, 0, st, (const bf16_t*)out, (const bf16_t*)dout, delta_ws, (int)batch, (int)n, (int)heads);
+            hipLaunchKernelGGL((attn_delta_kernel<bf16_t, 2>), dgrid, dblock, 0, st, (const bf16_t*)out, (const bf16_t*)dout, delta_ws, (int)batch, (int)n, (int)heads);
         else
-            hipLaunchKernelGGL((attn_delta_kernel<float, 2>), wgrid, wblock, 0, st, (const float*)out, (const float*)dout, delta_ws, (int)batch, (int)n, (int)heads);
-        const int nw = attn_waves(n);
-#define W(T) switch (nw) { case 1: launch_attn_bwd<T, 1, 2>(p, st); break; case 2: launch_attn_bwd<T, 2, 2>(p, st); break; \
-                           case 3: launch_attn_bwd<T, 3, 2>(p, st); break; default: launch_attn_bwd<T, 4, 2>(p, st); break; }
-        if (dtype == XCLIP_BF16) { W(bf16_t) } else { W(float) }
-#undef W
-        return check_launch(__func__);
-    }
-    if (dtype == XCLIP_BF16 && n <= A3_MAX_N && !tiled_only) {               // merged head-resident backward (computes delta itself)
-        XC_REQUIRE(scale > 0.f, "the head-resident kernels take the score maximum before scaling: scale must be positive");
+            hipLaunchKernelGGL((attn_delta_kernel<float, 2>), dgrid, dblock, 0, st, (const float*)out, (const float*)dout, delta_ws, (int)batch, (int)n, (int)heads);
+        by_dtype(dtype, [&](auto t) { by_waves(nw, [&](auto w) { launch_attn_bwd<typename decltype(t)::type, decltype(w)::value, 2>(p, st); }); });
+        break;
+    case ATTN_RESIDENT: {                                      // merged head-resident backward (computes delta itself)
         // the single-pass form (attention5.h) for the sequences it takes; XCLIP_ATTN_BWD=3 (measurement build) keeps the two-phase kernel for the A/B
         // (XCLIP_ATTN5_MIN=2: every sequence it can take, for the record of where it loses)
         // round 6: the streaming persistent form (attention6.h) for n = 256 / 257, XCLIP_ATTN_BWD=6 on the measurement build: correct on the
@@ -235,29 +249,21 @@ int xclip_attention_bwd(const void* qkv, const uint8_t* mask, const void* out, c
         // (measured: no effect on the backward -- its two work-groups are latency-bound chains that already overlap)
         static const int stag = measure_env("XCLIP_ATTN_STAGGER_BWD", 0);
         p.stagger_10ns = (attn3_bwd_lds_bytes((int)n) <= 80 * 1024 && batch * heads >= 1024) ? stag : 0;
-        if (causal) {
-            XC_ALLOW_LDS(attn3_bwd_kernel<true>, 160 * 1024);
-            hipLaunchKernelGGL(attn3_bwd_kernel<true>, dim3((unsigned)(batch * heads)), dim3(nwq * 64), attn3_bwd_lds_bytes((int)n), st, p);
-        } else {
-            XC_ALLOW_LDS(attn3_bwd_kernel<false>, 160 * 1024);
-            hipLaunchKernelGGL(attn3_bwd_kernel<false>, dim3((unsigned)(batch * heads)), dim3(nwq * 64), attn3_bwd_lds_bytes((int)n), st, p);
-        }
-        return check_launch(__func__);
+        by_causal(causal, [&](auto c) {
+            XC_ALLOW_LDS(attn3_bwd_kernel<decltype(c)::value>, 160 * 1024);
+            hipLaunchKernelGGL(attn3_bwd_kernel<decltype(c)::value>, hgrid, dim3(nwq * 64), attn3_bwd_lds_bytes((int)n), st, p);
+        });
+        break;
     }
-    dim3 dgrid((unsigned)((batch * n + 3) / 4)), dblock(256);
-    if (dtype == XCLIP_BF16)
-        hipLaunchKernelGGL((attn_delta_kernel<bf16_t>), dgrid, dblock, 0, st, (const bf16_t*)out, (const bf16_t*)dout, delta_ws, (int)batch, (int)n, (int)heads);
-    else
-        hipLaunchKernelGGL((attn_delta_kernel<float>), dgrid, dblock, 0, st, (const float*)out, (const float*)dout, delta_ws, (int)batch, (int)n, (int)heads);
-    const int nw = attn_waves(n);
-#define F(T) switch (nw) { case 1: launch_attn_bwd<T, 1>(p, st); break; case 2: launch_attn_bwd<T, 2>(p, st); break; \
-                           case 3: launch_attn_bwd<T, 3>(p, st); break; default: launch_attn_bwd<T, 4>(p, st); break; }
-    if (dtype == XCLIP_BF16 && tiled_only) { F(bf16_t) }
-    else if (dtype == XCLIP_BF16) {
-        switch (nw) { case 1: launch_attn2_bwd<1>(p, st); break; case 2: launch_attn2_bwd<2>(p, st); break;
-                      case 3: launch_attn2_bwd<3>(p, st); break; default: launch_attn2_bwd<4>(p, st); break; }
-    } else { F(float) }
-#undef F
+    case ATTN_TILED_BF16:
+    case ATTN_TILED:
+        by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+            hipLaunchKernelGGL((attn_delta_kernel<T>), dgrid, dblock, 0, st, (const T*)out, (const T*)dout, delta_ws, (int)batch, (int)n, (int)heads);
+        });
+        if (route == ATTN_TILED_BF16) by_waves(nw, [&](auto w) { launch_attn2_bwd<decltype(w)::value>(p, st); });
+        else by_dtype(dtype, [&](auto t) { by_waves(nw, [&](auto w) { launch_attn_bwd<typename decltype(t)::type, decltype(w)::value>(p, st); }); });
+        break;
+    }
     return check_launch(__func__);
 }
 
@@ -272,8 +278,7 @@ int xclip_attention_pool_fwd(const void* q, const void* kv, const uint8_t* mask,
     memset(&p, 0, sizeof(p));
     p.q = q; p.kv = kv; p.mask = mask; p.out = out; p.lse = lse;
     p.batch = (int)batch; p.n = (int)n; p.heads = (int)heads; p.nvis = (int)visible_keys; p.scale = scale;
-    if (dtype == XCLIP_BF16) launch_attn_pool<bf16_t>(p, head_dim, false, (hipStream_t)stream);
-    else launch_attn_pool<float>(p, head_dim, false, (hipStream_t)stream);
+    by_dtype(dtype, [&](auto t) { launch_attn_pool<typename decltype(t)::type>(p, head_dim, false, (hipStream_t)stream); });
     return check_launch(__func__);
 }
 
@@ -290,8 +295,7 @@ int xclip_attention_pool_bwd(const void* q, const void* kv, const uint8_t* mask,
     memset(&p, 0, sizeof(p));
     p.q = q; p.kv = kv; p.mask = mask; p.out = const_cast<void*>(out); p.lse = const_cast<float*>(lse); p.dout = dout; p.dq = dq; p.dkv = dkv;
     p.batch = (int)batch; p.n = (int)n; p.heads = (int)heads; p.nvis = (int)visible_keys; p.scale = scale;
-    if (dtype == XCLIP_BF16) launch_attn_pool<bf16_t>(p, head_dim, true, (hipStream_t)stream);
-    else launch_attn_pool<float>(p, head_dim, true, (hipStream_t)stream);
+    by_dtype(dtype, [&](auto t) { launch_attn_pool<typename decltype(t)::type>(p, head_dim, true, (hipStream_t)stream); });
     return check_launch(__func__);
 }
 
