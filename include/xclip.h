@@ -20,7 +20,7 @@ extern "C" {
 #endif
 
 enum { XCLIP_F32 = 0, XCLIP_BF16 = 1 };
-#define XCLIP_ABI_VERSION 27
+#define XCLIP_ABI_VERSION 28
 
 int xclip_abi_version(void);
 const char* xclip_last_error(void);
@@ -270,6 +270,30 @@ int xclip_simrank_partial(const void* Q, const void* K, int64_t nq, int64_t nk, 
 /* x_clip.py:813-847 */
 int xclip_simrank_combine(const void* workspace, int64_t nq, int64_t tile_slots, int32_t* rank, float* hard_val, int32_t* hard_idx,
                           void* stream);
+
+/* ---- retrieval / zero-shot classification: the k best columns of every row (the logits of x_clip.py:813-847, never stored) --------
+ * Same S, Q, K, scale and log_scale conventions as xclip_simloss_partial; 1 <= k <= 32.  A workspace of 5 * tile_slots * nq 4-byte
+ * values (xclip_simtopk_workspace_bytes for one chunk) holds, per row and 64-column slot, the three tables of xclip_simrank_partial
+ * and a 64-bit candidate mask.  Order of calls: (1) xclip_simrank_partial per chunk with thr = +inf and a diag_off no row reaches (the
+ * slot maxima); (2) `select`: tau[i] = the k-th largest slot maximum of row i (-3e38 if there are fewer than k slots) -- at least
+ * min(k, columns) logits of the row are >= tau[i], every top-k logit among them; (3) `mask` per chunk: the in-range columns with
+ * S_ij >= tau[i], formed by the loop of step 1, so with the same bits; (4) `finish` per chunk, in any order: every candidate's logit
+ * recomputed as xclip_simrank_pos forms it and merged into values / indices [nq, k], which the caller initialises to -3e38 / -1.
+ * Result: row-wise ordered by (value descending, global column = col0 + j ascending); rows with fewer than k scorable columns (a
+ * smaller gallery, NaN latents) keep -1 / -3e38 at the end.  No atomics anywhere: the same calls give the same bits.  The merge of step
+ * 4 is order-independent; the whole result is independent of the chunk cuts and their order where the logits are exact in fp32, and up
+ * to near-ties inside the fp32 accumulation error otherwise (tau follows the slot boundaries, and step 3 compares the tile loop's logit
+ * while step 4 ranks the re-scored one). */
+int64_t xclip_simtopk_workspace_bytes(int64_t nq, int64_t nk);
+/* x_clip.py:813-847 */
+int xclip_simtopk_select(const void* workspace, int64_t nq, int64_t tile_slots, int64_t k, float* tau, void* stream);
+/* x_clip.py:813-847 */
+int xclip_simtopk_mask(const void* Q, const void* K, int64_t nq, int64_t nk, int64_t d, float scale, const float* log_scale,
+                       const float* tau, void* workspace, int64_t tile_slot0, int64_t tile_slots, int dtype, void* stream);
+/* x_clip.py:813-847 */
+int xclip_simtopk_finish(const void* Q, const void* K, int64_t nq, int64_t nk, int64_t d, float scale, const float* log_scale,
+                         int64_t col0, const void* workspace, int64_t tile_slot0, int64_t tile_slots, int64_t k, float* values,
+                         int32_t* indices, int dtype, void* stream);
 
 /* ---- pairwise sigmoid loss (Zhai et al., "Sigmoid Loss for Language Image Pre-Training", 2023; the reference has none) ---------
  * Same Q, K, scale, log_scale and diag_off conventions as xclip_simloss_partial (diag_off is relative to the chunk); `bias` is a device

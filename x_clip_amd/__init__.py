@@ -7,6 +7,7 @@ Python host code (this package) over a C-ABI HIP library (include/xclip.h, built
 from .clip import CLIP, TextTransformer, VisionTransformer  # noqa: F401
 from .metrics import contrastive_metrics  # noqa: F401
 from .optim import FusedAdamW  # noqa: F401
+from .retrieval import similarity_topk, zero_shot_classifier  # noqa: F401
 
 
 def set_batch_invariant(on: bool = True) -> bool:
@@ -34,4 +35,5 @@ def set_batch_invariant(on: bool = True) -> bool:
 _small_limit_saved = None
 
 
-__all__ = ["CLIP", "TextTransformer", "VisionTransformer", "FusedAdamW", "contrastive_metrics", "set_batch_invariant"]
+__all__ = ["CLIP", "TextTransformer", "VisionTransformer", "FusedAdamW", "contrastive_metrics", "similarity_topk", "zero_shot_classifier",
+           "set_batch_invariant"]

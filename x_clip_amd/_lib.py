@@ -93,6 +93,10 @@ _SIGNATURES = {
     "xclip_simrank_pos": (c_int, [P, P, L, L, L, F, P, L, P, I, P]),
     "xclip_simrank_partial": (c_int, [P, P, L, L, L, F, P, L, L, P, P, L, L, I, P]),
     "xclip_simrank_combine": (c_int, [P, L, L, P, P, P, P]),
+    "xclip_simtopk_workspace_bytes": (c_int64, [L, L]),
+    "xclip_simtopk_select": (c_int, [P, L, L, L, P, P]),
+    "xclip_simtopk_mask": (c_int, [P, P, L, L, L, F, P, P, P, L, L, I, P]),
+    "xclip_simtopk_finish": (c_int, [P, P, L, L, L, F, P, L, P, L, L, L, P, P, I, P]),
     "xclip_sigloss_workspace_bytes": (c_int64, [L, L]),
     "xclip_sigloss_partial": (c_int, [P, P, L, L, L, F, P, P, L, P, L, L, I, P]),
     "xclip_sigloss_combine": (c_int, [P, L, L, P, P, F, P]),
@@ -102,7 +106,7 @@ _SIGNATURES = {
     "xclip_adamw_step": (c_int, [P, L, L, I, I, P, P, P, P, P, D, D, D, D, D, P]),
 }
 EXPORTS = tuple(_SIGNATURES)
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 
 def _bind(path: str):

@@ -473,6 +473,59 @@ class CLIP(nn.Module):
         self.last_metrics = None
         return self
 
+    def _no_single_latent(self, what):
+        if self.use_all_token_embeds:
+            raise NotImplementedError(f"CLIP.{what}: use_all_token_embeds (the fine-grained head) has no single latent per sample")
+
+    # ---- what forward and the one-tower entry points share (x_clip.py:650-715) ----
+    def _text_tower_call(self, text, text_mask, cls_row_only):
+        """-> (args, kwargs) of the text tower.  `cls_row_only`: the caller reads `enc_text[:, 0]` and nothing else (x_clip.py:708) -- the
+        tower is then asked for that row only and runs the row-wise part of its last layer on it (functional.stack_forward `pool_row`;
+        the same loss and gradients up to bf16 rounding order: the other rows of that part are dead in the forward and their gradient is
+        exactly zero in the backward).  `prune_unused_rows = False` keeps the dense last layer."""
+        text_args = (text,) if self.text_encode_without_mask else (text, text_mask)
+        text_kwargs = None
+        if (cls_row_only and self.prune_unused_rows and isinstance(self.text_transformer, TextTransformer) and self.text_has_cls_token
+                and not self.text_causal_mask):
+            text_kwargs = dict(pool_row=0)
+        return text_args, text_kwargs
+
+    def _join_text(self, enc_text_parts, text):
+        """the slices of _encode_text as one encoding, the EOS row in front under a causal mask (x_clip.py:670-685, its `b` is the batch size)"""
+        enc_text = enc_text_parts[0] if len(enc_text_parts) == 1 else torch.cat(enc_text_parts, dim=0)
+        if self.text_causal_mask:
+            enc_text = XF.eos_to_front(enc_text, text, self.text_eos_id)
+        return enc_text
+
+    def _text_cls_embeds(self, enc_text_parts, text):
+        """x_clip.py:708: row 0 of every sample (the slices are joined after that selection, not before, where nothing moves rows)"""
+        if len(enc_text_parts) > 1 and not self.text_causal_mask and enc_text_parts[0].ndim == 3:
+            return torch.cat([XF.select_row(e, 0) for e in enc_text_parts], dim=0)
+        enc_text = self._join_text(enc_text_parts, text)
+        return XF.select_row(enc_text, 0) if enc_text.ndim == 3 else enc_text
+
+    @staticmethod
+    def _image_cls_embeds(enc_image):
+        return XF.select_row(enc_image, 0) if enc_image.ndim == 3 else enc_image                 # x_clip.py:709
+
+    @torch.no_grad()
+    def embed_text(self, text):
+        """text [b, seq] token ids -> the l2-normalised text latents [b, dim_latent] alone: the text tower, the CLS row (the pooled
+        last layer where forward would use it), to_text_latent, l2norm -- in eval() mode the same bits as the text half of
+        forward(text, image, return_latents=True), without an image batch (x_clip.py:650-715, one side)."""
+        self._no_single_latent("embed_text")
+        text_args, text_kwargs = self._text_tower_call(text, text != self.text_pad_id, True)
+        text_embeds = self._text_cls_embeds(self._encode_text(text_args, False, text_kwargs), text)
+        return XF.l2norm(XF.linear(text_embeds, self.to_text_latent.weight))
+
+    @torch.no_grad()
+    def embed_image(self, image):
+        """image [b, c, h, w] -> the l2-normalised image latents [b, dim_latent] alone (the image half of
+        forward(text, image, return_latents=True), same bits in eval() mode; x_clip.py:650-715, one side)."""
+        self._no_single_latent("embed_image")
+        image_embeds = self._image_cls_embeds(self._encode_image(image, False))
+        return XF.l2norm(XF.linear(image_embeds, self.to_visual_latent.weight))
+
     def _side_stream(self, device, which=0):
         if device.type != "cuda":
             return None
@@ -580,16 +633,8 @@ class CLIP(nn.Module):
         assert not (not return_loss and is_multiview), 'do not pass in augmented texts or images if not training'
         assert not (self.multiview_loss_weight == 0 and is_multiview), 'multiview loss weight cannot be 0 if augmented text or images passed in'
 
-        text_args = (text,)
-        if not self.text_encode_without_mask:
-            text_args = (*text_args, text_mask)
-        # x_clip.py:708: the CLS path reads `enc_text[:, 0]` and nothing else -- the text tower is then asked for that row only and runs the
-        # row-wise part of its last layer on it (functional.stack_forward `pool_row`; the same loss and gradients up to bf16 rounding order: the other rows of that part
-        # are dead in the forward and their gradient is exactly zero in the backward).  `prune_unused_rows = False` keeps the dense last layer.
-        text_kwargs = None
-        if (self.prune_unused_rows and isinstance(self.text_transformer, TextTransformer) and self.text_has_cls_token
-                and not self.text_causal_mask and not self.use_all_token_embeds and not return_encodings):
-            text_kwargs = dict(pool_row=0)
+        cls_row_only = not self.use_all_token_embeds and not return_encodings               # x_clip.py:708 reads `enc_text[:, 0]` alone
+        text_args, text_kwargs = self._text_tower_call(text, text_mask, cls_row_only)
 
         # The two towers are independent until the head.  On a GPU the vision tower is issued on a side HIP stream (autograd
         # replays its backward there too), so its small kernels fill the gaps the text tower's leaves; the head waits for both.
@@ -605,28 +650,18 @@ class CLIP(nn.Module):
         else:
             enc_text_parts = self._encode_text(text_args, freeze_text_encoder, text_kwargs)
             enc_image = self._encode_image(image, freeze_image_encoder)
-        # (the CLS path below only needs row 0 of every sample: the slices are joined after that selection, not before)
-        cls_only = (len(enc_text_parts) > 1 and not self.text_causal_mask and not return_encodings and not self.use_all_token_embeds
-                    and enc_text_parts[0].ndim == 3)
-        enc_text = enc_text_parts[0] if (len(enc_text_parts) == 1 or cls_only) else torch.cat(enc_text_parts, dim=0)
-
-        if self.text_causal_mask:                                                          # x_clip.py:670-685 (its `b` is the batch size)
-            enc_text = XF.eos_to_front(enc_text, text, self.text_eos_id)
-
         if return_encodings:                                                               # x_clip.py:697-698
-            return enc_text, enc_image
+            return self._join_text(enc_text_parts, text), enc_image
 
         if self.use_all_token_embeds:                                                      # x_clip.py:702-706
+            enc_text = self._join_text(enc_text_parts, text)
             assert enc_text.ndim == 3, 'encoded text must have 3 dimensions (batch, seq, features)'
             assert enc_image.ndim == 3, 'encoded image must have 3 dimensions (batch, seq [height x width], features)'
             text_embeds = enc_text[:, 1:] if self.text_has_cls_token else enc_text
             image_embeds = enc_image[:, 1:] if self.visual_has_cls_token else enc_image
         else:                                                                              # x_clip.py:708-709
-            if cls_only:
-                text_embeds = torch.cat([XF.select_row(e, 0) for e in enc_text_parts], dim=0)
-            else:
-                text_embeds = XF.select_row(enc_text, 0) if enc_text.ndim == 3 else enc_text
-            image_embeds = XF.select_row(enc_image, 0) if enc_image.ndim == 3 else enc_image
+            text_embeds = self._text_cls_embeds(enc_text_parts, text)
+            image_embeds = self._image_cls_embeds(enc_image)
 
         text_latents = XF.l2norm(XF.linear(text_embeds, self.to_text_latent.weight))       # x_clip.py:713-715
         def visual_latents(proj):

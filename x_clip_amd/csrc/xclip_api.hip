@@ -22,6 +22,7 @@
 #include "kernels/simloss.h"
 #include "kernels/simloss5.h"
 #include "kernels/simrank.h"
+#include "kernels/simtopk.h"
 #include "kernels/sigloss.h"
 #include "kernels/sort.h"
 #include "kernels/tokens.h"
@@ -1516,6 +1517,52 @@ int xclip_simrank_combine(const void* workspace, int64_t nq, int64_t tile_slots,
     hipLaunchKernelGGL(simrank_combine_kernel, dim3((unsigned)((nq + 63) / 64)), dim3(1024), 3 * 16 * 64 * 4, (hipStream_t)stream, cnt,
                        (const float*)workspace + tile_slots * nq, (const int*)workspace + 2 * tile_slots * nq, rank, hard_val, hard_idx,
                        (int)nq, (int)tile_slots);
+    return check_launch(__func__);
+}
+
+// ---- retrieval / zero-shot top-k on the head's tile loop (kernels/simtopk.h; the logits of x_clip.py:813-847) ----
+// workspace: the rank partial's three tables (cnt, hmax, harg: the first sweep IS xclip_simrank_partial), then the two mask words
+int64_t xclip_simtopk_workspace_bytes(int64_t nq, int64_t nk) { return 5 * ((nk + 63) / 64) * nq * 4; }
+
+int xclip_simtopk_select(const void* workspace, int64_t nq, int64_t tile_slots, int64_t k, float* tau, void* stream) {
+    XC_REQUIRE(k >= 1 && k <= SIMTOPK_MAX_K, "k must lie in 1 .. 32");
+    XC_REQUIRE(nq > 0 && tile_slots > 0 && nq < (1LL << 31) && tile_slots < (1LL << 31) && workspace != nullptr && tau != nullptr, "bad arguments");
+    hipLaunchKernelGGL(simtopk_select_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                       (const float*)workspace + tile_slots * nq, tau, (int)nq, (int)tile_slots, (int)k);
+    return check_launch(__func__);
+}
+
+int xclip_simtopk_mask(const void* Q, const void* K, int64_t nq, int64_t nk, int64_t d, float scale, const float* log_scale,
+                       const float* tau, void* workspace, int64_t tile_slot0, int64_t tile_slots, int dtype, void* stream) {
+    XC_SIM_REQUIRE(sim_bad_args(Q, K, nq, nk, d, 0, dtype));
+    XC_REQUIRE(workspace != nullptr && tau != nullptr, "workspace and tau required");
+    XC_REQUIRE(tile_slot0 >= 0 && tile_slot0 + (nk + 63) / 64 <= tile_slots, "column slots out of range");
+    SimTopkParams p;
+    memset(&p, 0, sizeof(p));
+    // (diag_off: no row reaches it, so that every full tile takes the epilogue's plain form -- as in the first sweep)
+    p.s = sim_params(Q, K, nq, nk, d, scale, log_scale, -(1LL << 30), 0);
+    p.tau = tau;
+    p.mlo = (uint32_t*)workspace + (3 * tile_slots + tile_slot0) * nq;
+    p.mhi = (uint32_t*)workspace + (4 * tile_slots + tile_slot0) * nq;
+    sim_launch<SimTopkParams, sim5_mask_kernel, sim_mask_partial_kernel<bf16_t>, sim_mask_partial_kernel<float>>(p, p.s, dtype, (hipStream_t)stream);
+    return check_launch(__func__);
+}
+
+int xclip_simtopk_finish(const void* Q, const void* K, int64_t nq, int64_t nk, int64_t d, float scale, const float* log_scale,
+                         int64_t col0, const void* workspace, int64_t tile_slot0, int64_t tile_slots, int64_t k, float* values,
+                         int32_t* indices, int dtype, void* stream) {
+    XC_SIM_REQUIRE(sim_bad_args(Q, K, nq, nk, d, 0, dtype));
+    XC_REQUIRE(k >= 1 && k <= SIMTOPK_MAX_K, "k must lie in 1 .. 32");
+    XC_REQUIRE(workspace != nullptr && values != nullptr && indices != nullptr, "workspace, values and indices required");
+    XC_REQUIRE(col0 >= 0 && col0 + nk < (1LL << 31), "problem too large for 32-bit column indices");
+    XC_REQUIRE(tile_slot0 >= 0 && tile_slot0 + (nk + 63) / 64 <= tile_slots, "column slots out of range");
+    const uint32_t* mlo = (const uint32_t*)workspace + (3 * tile_slots + tile_slot0) * nq;
+    const uint32_t* mhi = (const uint32_t*)workspace + (4 * tile_slots + tile_slot0) * nq;
+    dim3 grid((unsigned)((nq + 3) / 4)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((simtopk_finish_kernel<T>), grid, block, 0, st, (const T*)Q, (const T*)K, (int)nq, (int)nk, (int)d, scale, log_scale, (int)col0, mlo, mhi, (int)k, values, indices);
+    });
     return check_launch(__func__);
 }
 

@@ -887,6 +887,85 @@ def simrank_chunked(q: Tensor, k_chunks, scale: float, diag_off: int, log_scale:
     return _chunked_head(q, k_chunks, before_chunk, 3, partial, combine, "sim_rank", neutral=neutral, stage=stage, extra_bytes=4 * nq)
 
 
+SIMTOPK_MAX_K = 32             # csrc/kernels/simtopk.h
+_NO_DIAGONAL = -(1 << 30)      # a diag_off no row reaches: nothing is excluded and every full tile takes the rank partial's plain form
+
+
+def simtopk(q: Tensor, k_mat: Tensor, k: int, scale: float, log_scale: Optional[Tensor] = None):
+    """S = scale * exp(log_scale) * q k_mat^T, never stored -> (values [nq, k] fp32, indices [nq, k] int32): per row the k best columns,
+    ordered by (value descending, column ascending); a row with fewer than k scorable columns (a smaller gallery, NaN latents) is padded
+    with index -1 / value -3e38 (the logits of x_clip.py:813-847)"""
+    return simtopk_chunked(q, [(k_mat, 0)], k, scale, log_scale)
+
+
+def simtopk_chunked(q: Tensor, k_chunks, k: int, scale: float, log_scale: Optional[Tensor] = None, before_chunk=None, debug: bool = False):
+    """Same result as simtopk(q, K, k) with K given as a LIST of (chunk [nk_c, d], first global column): the chunks are swept twice
+    (slot maxima, then the candidate masks against the row thresholds chosen from them), so a one-shot iterator will not do.  Cuts and
+    order of the list do not change the result where the logits are exact in fp32, and only among near-ties inside the fp32 accumulation
+    error otherwise (csrc/kernels/simtopk.h).  `before_chunk(c)` (optional) runs once per chunk, before it is first
+    touched (simloss_chunked_fwd).  Scratch: 5 4-byte words per (row, 64-column slot).
+    A gallery sharded over ranks needs nothing more: every rank calls this on its shard with its first global column and the
+    [nq, W * k] results are merged with a sort in torch.
+    debug=True: -> (values, indices, candidates [nq] int32: the set bits of every row's masks -- at least min(k, columns) each)."""
+    k_chunks = list(k_chunks)
+    k = int(k)
+    if not 1 <= k <= SIMTOPK_MAX_K:
+        raise ValueError(f"simtopk: k must lie in 1 .. {SIMTOPK_MAX_K}, got {k}")
+    _dev_check(q, *[kc for kc, _ in k_chunks], log_scale)
+    q = _c(q)
+    nq, d = q.shape
+    values = torch.full((nq, k), -3.0e38, dtype=torch.float32, device=q.device)
+    indices = torch.full((nq, k), -1, dtype=torch.int32, device=q.device)
+
+    def neutral():                                                  # every row is padding
+        return (values, indices, torch.zeros(nq, dtype=torch.int32, device=q.device)) if debug else (values, indices)
+
+    if nq == 0 or all(kc.shape[0] == 0 for kc, _ in k_chunks):      # nothing to score: no launch (the hooks still run)
+        for c in range(len(k_chunks) if before_chunk is not None else 0):
+            before_chunk(c)
+        return neutral()
+    L = _lib.lib()
+    sc, lsp = _scale_args(scale, log_scale)
+    code, st = dtype_code(q), _stream(q)
+    never = torch.full((nq,), float("inf"), dtype=torch.float32, device=q.device)
+    tau = torch.empty(nq, dtype=torch.float32, device=q.device)
+
+    def slot_max(kc, col0, slot0, slots, ws):
+        _lib.check(L.xclip_simrank_partial(q.data_ptr(), kc.data_ptr(), nq, kc.shape[0], d, sc, lsp, _NO_DIAGONAL, col0, never.data_ptr(),
+                                           ws.data_ptr(), slot0, slots, code, st), "xclip_simrank_partial")
+
+    def select(ws, slots):
+        _lib.check(L.xclip_simtopk_select(ws.data_ptr(), nq, slots, k, tau.data_ptr(), st), "xclip_simtopk_select")
+
+    _chunked_head(q, k_chunks, before_chunk, 5, slot_max, select, "sim_topk_max", neutral=neutral, extra_bytes=4 * nq)
+
+    # the second sweep: the same chunks, cuts, slots and workspace as the first (the same logit bits); each chunk's candidates are
+    # merged into the result as soon as its masks stand
+    def mask(kc, col0, slot0, slots, ws):
+        _lib.check(L.xclip_simtopk_mask(q.data_ptr(), kc.data_ptr(), nq, kc.shape[0], d, sc, lsp, tau.data_ptr(), ws.data_ptr(), slot0, slots,
+                                        code, st), "xclip_simtopk_mask")
+
+    def finish(ws, slots):
+        slot0 = 0
+        for kc, col0 in k_chunks:
+            kc = _c(kc)
+            nk = kc.shape[0]
+            if nk == 0:
+                continue
+            _lib.check(L.xclip_simtopk_finish(q.data_ptr(), kc.data_ptr(), nq, nk, d, sc, lsp, col0, ws.data_ptr(), slot0, slots, k,
+                                              values.data_ptr(), indices.data_ptr(), code, st), "xclip_simtopk_finish")
+            slot0 += (nk + 63) // 64
+        if not debug:
+            return values, indices
+        words = ws[3 * slots * nq * 4: 5 * slots * nq * 4].view(torch.int32).view(2 * slots, nq)
+        bits = torch.zeros(nq, dtype=torch.int32, device=q.device)
+        for b in range(32):
+            bits += ((words >> b) & 1).sum(0, dtype=torch.int32)
+        return values, indices, bits
+
+    return _chunked_head(q, k_chunks, None, 5, mask, finish, "sim_topk_mask", neutral=neutral, extra_bytes=4 * nq)
+
+
 def _g_out(q: Tensor, nk: int, out: Optional[Tensor], gmul: Optional[Tensor]):
     """-> G [nq, nk rounded up to the chunk] in q.dtype for a grad (`out` checked, or a new tensor) and its row length"""
     v = vec(q.dtype)
