@@ -433,3 +433,12 @@ def test_pruned_text_rows_inference_paths():
         outs.append((tl, il, sim, enc_t))
     for a, b in zip(*outs):
         torch.testing.assert_close(a, b, rtol=1e-5, atol=1e-6)
+
+
+@pytest.mark.parametrize("checkpoint", [False, True], ids=["tape", "checkpoint"])
+@pytest.mark.parametrize("row", [0, 4, 9])
+@pytest.mark.parametrize("rotary,causal", [(False, False), (True, False), (False, True), (True, True)], ids=["plain", "rotary", "causal", "rotary_causal"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_pool_row_equals_dense_row(dtype, rotary, causal, row, checkpoint):
+    """text_encode(pool_row=r) for the first, a middle and the last row of 9 tokens + CLS: the pooled last layer against row r of the dense one"""
+    C.case_pool_row_equals_dense_row(DEV, dtype, rotary, causal, row, checkpoint, B=3, dim=64, heads=2, dim_head=32, n_tok=9)

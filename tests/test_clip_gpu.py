@@ -70,6 +70,16 @@ def test_pruned_text_rows_equal_dense_last_layer(dtype):
     C.case_pruned_rows_equal_dense(DEV, dtype, O.ClipConfig(num_text_tokens=3000), 24)
 
 
+@pytest.mark.parametrize("checkpoint", [False, True], ids=["tape", "checkpoint"])
+@pytest.mark.parametrize("row", [0, 7, 32])
+@pytest.mark.parametrize("rotary,causal", [(False, False), (True, False), (False, True), (True, True)], ids=["plain", "rotary", "causal", "rotary_causal"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_pool_row_equals_dense_row(dtype, rotary, causal, row, checkpoint):
+    """text_encode(pool_row=r) for the first, a middle and the last row of 32 tokens + CLS (one whole 32-block of keys plus a tail row, a key
+    count that is no multiple of the pooled kernel's keys per wave-load): the pooled last layer against row r of the dense one"""
+    C.case_pool_row_equals_dense_row(DEV, dtype, rotary, causal, row, checkpoint, B=5, dim=128, heads=2, dim_head=64, n_tok=32)
+
+
 # ---- the HEADLINE architecture (what bench.py times: O.ClipConfig() defaults = depth 6 / 6, text length 256 -> 257 positions, 64
 # patches of which 32 are kept) against the fp64 oracle, every parameter gradient in full ---------------------------------------------
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])

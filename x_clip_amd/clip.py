@@ -132,11 +132,11 @@ class Transformer(nn.Module):
         dh, h = self.dim_head, self.heads
         for attn, ff in self.layers:
             w_qkv, w_out = attn.fn.to_qkv.weight, attn.fn.to_out[0].weight
-            hs = 64 if dh <= 64 else 128                      # the kernels' head slot (StackSpec.head_slot)
+            hs = XF.head_slot(dh)                             # the kernels' head slot
             if dh < hs:                                       # heads narrower than their slot: zero rows / columns (StackSpec)
                 w_qkv, w_out = self._padded(w_qkv, w_out, dh, h, hs)
-            ps += [attn.norm.g, w_qkv, w_out, attn.fn.to_out[1].g,
-                   ff.norm.g, ff.fn.net[0].weight, ff.fn.net[2].g, ff.fn.net[4].weight]
+            ps += XF.LayerWeights(g_attn=attn.norm.g, w_qkv=w_qkv, w_out=w_out, g_out=attn.fn.to_out[1].g,
+                                  g_ff=ff.norm.g, w_ff1=ff.fn.net[0].weight, g_inner=ff.fn.net[2].g, w_ff2=ff.fn.net[4].weight)
         ps.append(self.norm_out.g)
         return ps
 

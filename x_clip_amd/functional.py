@@ -17,7 +17,7 @@ inputs of a layer and re-runs that layer's forward inside the backward.
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -81,20 +81,13 @@ class _SideGemm:
 
     def wgrad(self, dy: Tensor, x: Tensor, N1: int, N2: int, M: int, w: Optional[Tensor] = None) -> Tensor:
         """dW [N1, N2] = dy^T x (contraction over the M token rows), issued on the side stream; `w`: the weight it is the gradient of"""
-        out = _grad_out(w, (N1, N2), dy.dtype, dy.device)             # main-stream memory (or a bucket slice): consumed after join()
-        if self.side is None:
-            return ops.gemm(dy, x, N1, N2, M, a_kmajor=True, b_kmajor=True, out=out)
-        self.side.wait_stream(self.main)                     # dy was just produced on the main stream
-        with torch.cuda.stream(self.side):
-            ops.gemm(dy, x, N1, N2, M, a_kmajor=True, b_kmajor=True, out=out)
-        self.keep.append((dy, x))
-        return out
+        return self.wgrad_into(dy, x, N1, N2, M, _grad_out(w, (N1, N2), dy.dtype, dy.device))   # main-stream memory (or a bucket slice): consumed after join()
 
     def wgrad_into(self, dy: Tensor, x: Tensor, N1: int, N2: int, M: int, out: Tensor) -> Tensor:
         """the same product written into a given [N1, N2] view (a row block of a weight gradient assembled from two products)"""
         if self.side is None:
             return ops.gemm(dy, x, N1, N2, M, a_kmajor=True, b_kmajor=True, out=out)
-        self.side.wait_stream(self.main)
+        self.side.wait_stream(self.main)                     # dy was just produced on the main stream
         with torch.cuda.stream(self.side):
             ops.gemm(dy, x, N1, N2, M, a_kmajor=True, b_kmajor=True, out=out)
         self.keep.append((dy, x))
@@ -122,7 +115,23 @@ def _draw_seed() -> int:
     return int(torch.randint(0, 1 << 62, (1,), dtype=torch.int64).item())
 
 
-LAYER_PARAMS = 8          # attn_norm.g, to_qkv.w, to_out.w, to_out_norm.g, ff_norm.g, ff1.w, ff_inner_norm.g, ff2.w
+# One layer's parameters in their flat order (clip.Transformer.stack_params): attn_norm.g, to_qkv.w, to_out.0.w, to_out.1.g, ff_norm.g, net.0.w, net.2.g, net.4.w
+LayerWeights = NamedTuple("LayerWeights", [(f, Tensor) for f in "g_attn w_qkv w_out g_out g_ff w_ff1 g_inner w_ff2".split()])
+LAYER_PARAMS = len(LayerWeights._fields)
+IS_GAIN = tuple(f.startswith("g_") for f in LayerWeights._fields)       # LayerNorm gains (_GainGrads); the others are GEMM weights (_SideGemm.wgrad)
+# What a layer's backward reads (m*, r*: LayerNorm statistics; qkv / o: the packed rotated qkv and the attention output, or the one-query
+# pooled layer's (q, kv) and pooled output; p: to_out.0's output; x1: the stream between the blocks; a: what net.4 saw)
+LayerTape = NamedTuple("LayerTape", [(f, object) for f in "x h m1 r1 qkv o lse p m2 r2 x1 h2 m3 r3 u a m4 r4".split()])
+
+
+def layer_weights(flat: Sequence, l: int):
+    """(layer l's entries by name, their offset) of the flat params norm_in.g, depth x LayerWeights, norm_out.g -- or of a list aligned with them"""
+    base = 1 + LAYER_PARAMS * l
+    return LayerWeights._make(flat[base: base + LAYER_PARAMS]), base
+
+
+def head_slot(dim_head: int) -> int:        # features per head slot in the packed qkv / attention output: 64, or 128 for heads wider than 64
+    return 64 if dim_head <= 64 else 128
 
 
 @dataclass(frozen=True)
@@ -148,94 +157,132 @@ class StackSpec:
 
     @property
     def head_slot(self) -> int:
-        """features per head slot in the packed qkv / attention output: 64, or 128 for heads wider than 64"""
-        return 64 if self.dim_head <= 64 else 128
+        return head_slot(self.dim_head)
+
+    @property
+    def inner(self) -> int:                 # width of the packed attention output
+        return self.heads * self.head_slot
+
+    @property
+    def scale(self) -> float:
+        return self.dim_head ** -0.5
 
 
 class _GainGrads:
-    """All LayerNorm gain gradients of one backward share a flat fp32 accumulator (the LN backward kernels add into
-    it with atomics) and are converted to the parameter dtype by one cast launch at the end."""
+    """All LayerNorm gain gradients of one backward share a flat fp32 accumulator (the LN backward kernels add into it with atomics) and are
+    converted to the parameter dtype by one cast launch at the end.  `views`: the accumulators, aligned with the parameter list (None elsewhere)"""
 
-    def __init__(self, gains: Sequence[Tensor]):
-        self.sizes = [g.numel() for g in gains]
-        self.dtype = gains[0].dtype
-        self.flat = torch.zeros(sum(self.sizes), dtype=torch.float32, device=gains[0].device)
-        self.views = list(self.flat.split(self.sizes))
+    def __init__(self, params: Sequence[Tensor], is_gain: Sequence[bool]):
+        self.at = [i for i, g in enumerate(is_gain) if g]
+        self.sizes = [params[i].numel() for i in self.at]
+        self.dtype = params[0].dtype
+        self.flat = torch.zeros(sum(self.sizes), dtype=torch.float32, device=params[0].device)
+        self.views = self._put(self.flat, [None] * len(params))
 
-    def finish(self) -> List[Tensor]:
-        if self.dtype == torch.float32:
-            return self.views
-        return list(ops.cast_from_f32(self.flat, self.dtype).split(self.sizes))
+    def _put(self, flat: Tensor, out: list) -> list:
+        for i, v in zip(self.at, flat.split(self.sizes)):
+            out[i] = v
+        return out
+
+    def finish(self, grads: list) -> None:                      # the finished gain gradients into their places in `grads`
+        self._put(self.flat if self.dtype == torch.float32 else ops.cast_from_f32(self.flat, self.dtype), grads)
 
 
-# ---- one pre-norm residual block pair (x_clip.py:285-289) --------------------------------------------------------------
-def _layer_forward(x: Tensor, B: int, n: int, W: Sequence[Tensor], heads: int, mask: Optional[Tensor], rotary: Optional[Tensor] = None,
-                   causal: bool = False, scale: float = 0.125, hs: int = 64, drop=(0.0, 0.0, 0)):
-    g_attn, w_qkv, w_out, g_out, g_ff, w_ff1, g_inner, w_ff2 = W
+# ---- one pre-norm residual block pair (x_clip.py:285-289): the attention block and the feed-forward block -----------------------------
+# c: what a pass shares; seed: the layer's dropout seed (+ 1: the feed-forward block's); need / dg: the layer's `need` flags / gain accumulators
+_Pass = NamedTuple("_Pass", [("spec", StackSpec), ("B", int), ("n", int), ("mask", Optional[Tensor])])
+
+
+def _attn_forward(h: Tensor, W: LayerWeights, c: _Pass, seed: int):
+    """the dense attention behind the PreNorm output h [B n, D] -> (packed qkv as the kernels read it, attention output, log-sum-exp)"""
+    M, D = h.shape
+    spec, inner = c.spec, c.spec.inner
+    qkv = ops.gemm(h, W.w_qkv, M, 3 * inner, D)                                        # to_qkv            :216
+    if spec.rotary is not None:
+        ops.rotary_(qkv, c.n, spec.rotary, head_dim=spec.head_slot)                    # q, k, v rotated   :221-223
+    o, lse = ops.attention_fwd(qkv.view(c.B, c.n, 3 * inner), c.mask, spec.heads, spec.scale, spec.causal, spec.head_slot, spec.attn_dropout, seed)   # :217-244
+    return qkv, o, lse
+
+
+def _ffn_forward(p: Tensor, x: Tensor, W: LayerWeights, c: _Pass, seed: int):
+    """to_out.0's output p and the residual stream x, on whatever rows they hold -> (the layer output, the tape's fields from m2 on)"""
     M, D = x.shape
-    inner = heads * hs                                                                 # hs: features per head slot (64 | 128)
-    p_attn, p_ff, seed = drop                                                          # dropout probabilities, this layer's seed
-    h, m1, r1 = ops.layernorm_fwd(x, g_attn)                                           # PreNorm           :126
-    qkv = ops.gemm(h, w_qkv, M, 3 * inner, D)                                          # to_qkv            :216
-    if rotary is not None:
-        ops.rotary_(qkv, n, rotary, head_dim=hs)                                               # q, k, v rotated   :221-223
-    o, lse = ops.attention_fwd(qkv.view(B, n, 3 * inner), mask, heads, scale, causal, hs, p_attn, seed)   # scale/mask/softmax(/dropout) :217-244
-    p = ops.gemm(o.view(M, inner), w_out, M, D, inner)                                 # to_out.0          :245
-    x1, m2, r2, h2, m3, r3 = ops.layernorm_chain_fwd(p, g_out, x, g_ff)                # to_out.1 + skip :245,288 and PreNorm :126, one pass
-    u = ops.gemm(h2, w_ff1, M, w_ff1.shape[0], D)                                      # net.0             :191
-    a, m4, r4 = ops.layernorm_fwd(u, g_inner, geglu=True)                              # GEGLU + net.2     :192-193
-    if p_ff > 0.0:
-        ops.dropout(a, p_ff, seed + 1, out=a)                                          # net.3 Dropout     :194 (in place: `a` is only read by net.4)
-    x2 = ops.gemm(a, w_ff2, M, D, a.shape[1], residual=x1)                             # net.4 + skip      :195,289
-    return x2, (x, h, m1, r1, qkv, o, lse, p, m2, r2, x1, h2, m3, r3, u, a, m4, r4)
+    x1, m2, r2, h2, m3, r3 = ops.layernorm_chain_fwd(p, W.g_out, x, W.g_ff)            # to_out.1 + skip :245,288 and PreNorm :126, one pass
+    u = ops.gemm(h2, W.w_ff1, M, W.w_ff1.shape[0], D)                                  # net.0             :191
+    a, m4, r4 = ops.layernorm_fwd(u, W.g_inner, geglu=True)                            # GEGLU + net.2     :192-193
+    if c.spec.ff_dropout > 0.0:
+        ops.dropout(a, c.spec.ff_dropout, seed + 1, out=a)                             # net.3 Dropout     :194 (in place: `a` is only read by net.4)
+    x2 = ops.gemm(a, W.w_ff2, M, D, a.shape[1], residual=x1)                           # net.4 + skip      :195,289
+    return x2, dict(m2=m2, r2=r2, x1=x1, h2=h2, m3=m3, r3=r3, u=u, a=a, m4=m4, r4=r4)
 
 
-def _layer_backward(dx2: Tensor, saved, B: int, n: int, W: Sequence[Tensor], heads: int, mask: Optional[Tensor],
-                    gain_acc: Sequence[Tensor], need_w: Sequence[bool], sg: "_SideGemm", rotary: Optional[Tensor] = None,
-                    causal: bool = False, scale: float = 0.125, hs: int = 64, drop=(0.0, 0.0, 0), x2: Optional[Tensor] = None,
-                    rowc: Optional[Tensor] = None, below=None):
-    """dx2: gradient w.r.t. the layer output [M, D] -> (gradient w.r.t. the layer input, [dWqkv, dWout, dWff1, dWff2]).
-    x2 = the layer's output (the next layer's saved input): with it the feed-forward block's first two backward steps run as one kernel;
-    rowc = that kernel's per-row constants when the pass that produced dx2 already wrote them (ops.layernorm_bwd(ffn_stats=...));
-    below = the same request for the layer BELOW this one (ops.ffn_stats_request): this layer's last kernel writes its input gradient"""
-    p_attn, p_ff, seed = drop
-    g_attn, w_qkv, w_out, g_out, g_ff, w_ff1, g_inner, w_ff2 = W
-    dg_attn, dg_out, dg_ff, dg_inner = gain_acc
-    x, h, m1, r1, qkv, o, lse, p, m2, r2, x1, h2, m3, r3, u, a, m4, r4 = saved
+def _layer_forward(x: Tensor, W: LayerWeights, c: _Pass, seed: int):
     M, D = x.shape
-    inner = heads * hs
-    F2 = w_ff1.shape[0]
-    Fh = F2 // 2
-    # feed-forward block
+    h, m1, r1 = ops.layernorm_fwd(x, W.g_attn)                                         # PreNorm           :126
+    qkv, o, lse = _attn_forward(h, W, c, seed)
+    p = ops.gemm(o.view(M, c.spec.inner), W.w_out, M, D, c.spec.inner)                 # to_out.0          :245
+    x2, ff = _ffn_forward(p, x, W, c, seed)
+    return x2, LayerTape(x=x, h=h, m1=m1, r1=r1, qkv=qkv, o=o, lse=lse, p=p, **ff)
+
+
+def _ffn_backward(dx2: Tensor, t: LayerTape, W: LayerWeights, need: LayerWeights, dg: LayerWeights, c: _Pass, sg: _SideGemm, seed: int, x2=None, rowc=None):
+    """dx2: gradient w.r.t. the layer output, on the rows the feed-forward block ran on -> (gradient w.r.t. x1 through the skip and the
+    PreNorm, gradient w.r.t. to_out.0's output p, dWff1, dWff2).  x2 / rowc: see _layer_backward; without them the two-kernel form"""
+    M, D = dx2.shape
+    F2, Fh, p_ff = W.w_ff1.shape[0], W.w_ff1.shape[0] // 2, c.spec.ff_dropout
     if (x2 is not None or rowc is not None) and p_ff == 0.0 and ops.ffn_dgrad_geglu_ok(M, Fh, D, dx2.dtype):
         # net.4's input gradient and net.2's (GEGLU-LayerNorm) backward in one kernel: d a never reaches memory (csrc/kernels/gemm9.h)
-        du, _ = ops.ffn_dgrad_geglu(dx2, w_ff2, u, g_inner, m4, r4, x2, x1, dg=dg_inner, rowc=rowc)
-        d_ff2 = sg.wgrad(dx2, a, D, Fh, M, w_ff2) if need_w[3] else None
+        du, _ = ops.ffn_dgrad_geglu(dx2, W.w_ff2, t.u, W.g_inner, t.m4, t.r4, x2, t.x1, dg=dg.g_inner, rowc=rowc)
+        d_ff2 = sg.wgrad(dx2, t.a, D, Fh, M, W.w_ff2) if need.w_ff2 else None
     else:
-        da = ops.gemm(dx2, w_ff2, M, Fh, D, b_kmajor=True)
-        d_ff2 = sg.wgrad(dx2, a, D, Fh, M, w_ff2) if need_w[3] else None      # (`a` is the dropped activation: what net.4 saw)
+        da = ops.gemm(dx2, W.w_ff2, M, Fh, D, b_kmajor=True)
+        d_ff2 = sg.wgrad(dx2, t.a, D, Fh, M, W.w_ff2) if need.w_ff2 else None     # (`a` is the dropped activation: what net.4 saw)
         if p_ff > 0.0:
             ops.dropout(da, p_ff, seed + 1, out=da)                                         # the same mask on the gradient
-        du, _ = ops.layernorm_bwd(da, u, g_inner, m4, r4, geglu=True, dg=dg_inner)
+        du, _ = ops.layernorm_bwd(da, t.u, W.g_inner, t.m4, t.r4, geglu=True, dg=dg.g_inner)
         del da
-    dh2 = ops.gemm(du, w_ff1, M, D, F2, b_kmajor=True)
-    d_ff1 = sg.wgrad(du, h2, F2, D, M, w_ff1) if need_w[2] else None
+    dh2 = ops.gemm(du, W.w_ff1, M, D, F2, b_kmajor=True)
+    d_ff1 = sg.wgrad(du, t.h2, F2, D, M, W.w_ff1) if need.w_ff1 else None
     del du
     # PreNorm backward + skip, then to_out's LayerNorm backward (the attention block), one pass over the rows
-    dx1, dp = ops.layernorm_chain_bwd(dh2, x1, g_ff, m3, r3, dx2, p, g_out, m2, r2, dg_ff, dg_out)
+    dx1, dp = ops.layernorm_chain_bwd(dh2, t.x1, W.g_ff, t.m3, t.r3, dx2, t.p, W.g_out, t.m2, t.r2, dg.g_ff, dg.g_out)
     del dh2
-    do = ops.gemm(dp, w_out, M, inner, D, b_kmajor=True)
-    d_out = sg.wgrad(dp, o.view(M, inner), D, inner, M, w_out) if need_w[1] else None
+    return dx1, dp, d_ff1, d_ff2
+
+
+def _attn_backward(do: Tensor, t: LayerTape, c: _Pass, seed: int) -> Tensor:
+    """the dense attention: gradient w.r.t. its output [M, inner] -> gradient w.r.t. the packed rotated qkv [M, 3 inner]"""
+    spec, B, n, inner = c.spec, c.B, c.n, c.spec.inner
+    dqkv = ops.attention_bwd(t.qkv.view(B, n, 3 * inner), c.mask, t.o, do.view(B, n, inner), t.lse, spec.heads, spec.scale, spec.causal, spec.head_slot, spec.attn_dropout, seed)
+    return dqkv.view(B * n, 3 * inner)
+
+
+def _qkv_backward(dqkv: Tensor, t: LayerTape, W: LayerWeights, need: LayerWeights, c: _Pass, sg: _SideGemm):
+    """gradient w.r.t. the packed rotated qkv (rotated back in place) -> (gradient w.r.t. the PreNorm output h, dWqkv)"""
+    (M, D), N = t.h.shape, dqkv.shape[1]
+    if c.spec.rotary is not None:
+        ops.rotary_(dqkv, c.n, c.spec.rotary, inverse=True, head_dim=c.spec.head_slot)      # the saved qkv is the rotated one; R^T maps its gradient back
+    dh = ops.gemm(dqkv, W.w_qkv, M, D, N, b_kmajor=True)
+    return dh, sg.wgrad(dqkv, t.h, N, D, M, W.w_qkv) if need.w_qkv else None
+
+
+def _layer_backward(dx2: Tensor, t: LayerTape, W: LayerWeights, need: LayerWeights, dg: LayerWeights, c: _Pass, sg: _SideGemm, seed: int,
+                    x2: Tensor, stats=(None, None)):
+    """dx2: gradient w.r.t. the layer output [M, D] -> (gradient w.r.t. the layer input, the weight gradients by field name).
+    x2 = the layer's output (the next layer's saved input): with it the feed-forward block's first two backward steps run as one kernel; stats = (rowc, below): that kernel's
+    per-row constants when the pass that produced dx2 already wrote them (ops.layernorm_bwd(ffn_stats=...)), and ops.ffn_stats_request for the layer BELOW, whose dx2 this one writes"""
+    M, D = dx2.shape
+    rowc, below = stats
+    dx1, dp, d_ff1, d_ff2 = _ffn_backward(dx2, t, W, need, dg, c, sg, seed, x2, rowc)
+    do = ops.gemm(dp, W.w_out, M, c.spec.inner, D, b_kmajor=True)
+    d_out = sg.wgrad(dp, t.o.view(M, c.spec.inner), D, c.spec.inner, M, W.w_out) if need.w_out else None
     del dp
-    dqkv = ops.attention_bwd(qkv.view(B, n, 3 * inner), mask, o, do.view(B, n, inner), lse, heads, scale, causal, hs, p_attn, seed)
+    dqkv = _attn_backward(do, t, c, seed)
     del do
-    if rotary is not None:
-        ops.rotary_(dqkv.view(M, 3 * inner), n, rotary, inverse=True, head_dim=hs)      # the saved qkv is the rotated one; R^T maps its gradient back
-    dh = ops.gemm(dqkv.view(M, 3 * inner), w_qkv, M, D, 3 * inner, b_kmajor=True)
-    d_qkv = sg.wgrad(dqkv.view(M, 3 * inner), h, 3 * inner, D, M, w_qkv) if need_w[0] else None
+    dh, d_qkv = _qkv_backward(dqkv, t, W, need, c, sg)
     del dqkv
-    dx, _ = ops.layernorm_bwd(dh, x, g_attn, m1, r1, dres=dx1, dg=dg_attn, ffn_stats=below)
-    return dx, [d_qkv, d_out, d_ff1, d_ff2]
+    dx, _ = ops.layernorm_bwd(dh, t.x, W.g_attn, t.m1, t.r1, dres=dx1, dg=dg.g_attn, ffn_stats=below)
+    return dx, dict(w_qkv=d_qkv, w_out=d_out, w_ff1=d_ff1, w_ff2=d_ff2)
 
 
 # ---- the LAST layer when only one token row per sample leaves the stack (the CLS row: x_clip.py:708 `enc_text[:, 0]`) -----------------
@@ -247,101 +294,77 @@ def _layer_backward(dx2: Tensor, saved, B: int, n: int, W: Sequence[Tensor], hea
 # fp32; in bf16 the pooled rows' gradients are rounded at other points than in the dense layer (the LayerNorm backward's dx and the skip
 # gradient are added as two bf16 tensors where the dense kernel fuses them in fp32; dh is the sum of two rounded products where the dense layer
 # takes one contraction over 3 inner), so toggling `prune_unused_rows` moves results by bf16 ulps -- the tests hold pooled against dense to the
-# bars of the dense layer against the oracle, not to bit equality.
+# bars of the dense layer against the oracle, not to bit equality.  No dropout here (can_pool): the shared blocks get the seed 0.
 def _pool_view(t2d: Tensor, B: int, n: int, row: int) -> Tensor:
     """rows b n + row of a contiguous [B n, W] tensor as a [B, W] view (row stride n W)"""
     Wd = t2d.shape[1]
     return t2d.view(B, n * Wd)[:, row * Wd:(row + 1) * Wd]
 
 
-def _layer_forward_pooled(x: Tensor, B: int, n: int, W: Sequence[Tensor], heads: int, mask: Optional[Tensor], rotary: Optional[Tensor],
-                          causal: bool, scale: float, hs: int, row: int):
-    g_attn, w_qkv, w_out, g_out, g_ff, w_ff1, g_inner, w_ff2 = W
+def _add_to_pooled_rows(full: Tensor, add: Tensor, B: int, n: int, row: int) -> None:
+    """full[b n + row] += add[b]: the pooled rows copied out, added, copied back"""
+    rows = _pool_view(full, B, n, row)
+    t = torch.empty(B, full.shape[1], dtype=full.dtype, device=full.device)
+    ops.copy_rows(rows, t)
+    ops.copy_rows(ops.add_rows(t, add), rows)
+
+
+def _layer_forward_pooled(x: Tensor, W: LayerWeights, c: _Pass, row: int):
+    spec, B, n, inner = c.spec, c.B, c.n, c.spec.inner
     M, D = x.shape
-    inner = heads * hs
-    h, m1, r1 = ops.layernorm_fwd(x, g_attn)
+    h, m1, r1 = ops.layernorm_fwd(x, W.g_attn)
     xc = torch.empty(B, D, dtype=x.dtype, device=x.device)
     ops.copy_rows(_pool_view(x, B, n, row), xc)                                        # the skip connection's pooled rows
-    if rotary is None or row == 0:
-        # one query per head: to_qkv's first third on the pooled rows, the other two on every row, attention_pool.h (causal: the pooled
-        # row sees the keys up to itself).  Rotary encoders: keys and values are rotated at their positions; the query at position 0 is
-        # rotated by the angle 0 -- the identity (x_clip.py:155-176,221-223)
-        q = ops.gemm(_pool_view(h, B, n, row), w_qkv[:inner], B, inner, D)
-        kv = ops.gemm(h, w_qkv[inner:], M, 2 * inner, D)
-        if rotary is not None:
-            ops.rotary_(kv, n, rotary, head_dim=hs)
-        oc, lse = ops.attention_pool_fwd(q, kv.view(B, n, 2 * inner), mask, heads, scale, hs, row + 1 if causal else None)
-        qkv, o = (q, kv), oc                                                           # (the tape's qkv / o slots: the pooled forms)
-    else:
-        # (the rotary kernel walks whole packed qkv rows: the dense attention, then its pooled rows)
-        qkv = ops.gemm(h, w_qkv, M, 3 * inner, D)
-        ops.rotary_(qkv, n, rotary, head_dim=hs)
-        o, lse = ops.attention_fwd(qkv.view(B, n, 3 * inner), mask, heads, scale, causal, hs, 0.0, 0)
+    if spec.rotary is None or row == 0:
+        # one query per head: to_qkv's first third on the pooled rows, the other two on every row, attention_pool.h (causal: the pooled row sees the keys
+        # up to itself).  Rotary: keys and values are rotated at their positions; the query at position 0 by the angle 0 -- the identity (x_clip.py:155-176)
+        q = ops.gemm(_pool_view(h, B, n, row), W.w_qkv[:inner], B, inner, D)
+        kv = ops.gemm(h, W.w_qkv[inner:], M, 2 * inner, D)
+        if spec.rotary is not None:
+            ops.rotary_(kv, n, spec.rotary, head_dim=spec.head_slot)
+        oc, lse = ops.attention_pool_fwd(q, kv.view(B, n, 2 * inner), c.mask, spec.heads, spec.scale, spec.head_slot, row + 1 if spec.causal else None)
+        qkv, o = (q, kv), oc                                                           # (the tape's qkv / o fields: the pooled forms)
+    else:                                                      # (the rotary kernel walks whole packed qkv rows: the dense attention, then its pooled rows)
+        qkv, o, lse = _attn_forward(h, W, c, 0)
         oc = _pool_view(o.view(M, inner), B, n, row)
-    p = ops.gemm(oc, w_out, B, D, inner)                                               # from here on: B rows
-    x1, m2, r2, h2, m3, r3 = ops.layernorm_chain_fwd(p, g_out, xc, g_ff)
-    u = ops.gemm(h2, w_ff1, B, w_ff1.shape[0], D)
-    a, m4, r4 = ops.layernorm_fwd(u, g_inner, geglu=True)
-    x2 = ops.gemm(a, w_ff2, B, D, a.shape[1], residual=x1)
-    return x2, (x, h, m1, r1, qkv, o, lse, p, m2, r2, x1, h2, m3, r3, u, a, m4, r4)
+    p = ops.gemm(oc, W.w_out, B, D, inner)                                             # from here on: B rows
+    x2, ff = _ffn_forward(p, xc, W, c, 0)
+    return x2, LayerTape(x=x, h=h, m1=m1, r1=r1, qkv=qkv, o=o, lse=lse, p=p, **ff)
 
 
-def _layer_backward_pooled(dx2: Tensor, saved, B: int, n: int, W: Sequence[Tensor], heads: int, mask: Optional[Tensor],
-                           gain_acc: Sequence[Tensor], need_w: Sequence[bool], sg: "_SideGemm", rotary: Optional[Tensor], causal: bool,
-                           scale: float, hs: int, row: int):
+def _layer_backward_pooled(dx2: Tensor, t: LayerTape, W: LayerWeights, need: LayerWeights, dg: LayerWeights, c: _Pass, sg: _SideGemm, row: int):
     """dx2 [B, D]: gradient w.r.t. the pooled rows of the layer output -> (gradient w.r.t. the layer input [B n, D], weight gradients)"""
-    g_attn, w_qkv, w_out, g_out, g_ff, w_ff1, g_inner, w_ff2 = W
-    dg_attn, dg_out, dg_ff, dg_inner = gain_acc
-    x, h, m1, r1, qkv, o, lse, p, m2, r2, x1, h2, m3, r3, u, a, m4, r4 = saved
-    M, D = x.shape
-    inner = heads * hs
-    F2 = w_ff1.shape[0]
-    Fh = F2 // 2
-    da = ops.gemm(dx2, w_ff2, B, Fh, D, b_kmajor=True)
-    d_ff2 = sg.wgrad(dx2, a, D, Fh, B, w_ff2) if need_w[3] else None
-    du, _ = ops.layernorm_bwd(da, u, g_inner, m4, r4, geglu=True, dg=dg_inner)
-    dh2 = ops.gemm(du, w_ff1, B, D, F2, b_kmajor=True)
-    d_ff1 = sg.wgrad(du, h2, F2, D, B, w_ff1) if need_w[2] else None
-    dx1, dp = ops.layernorm_chain_bwd(dh2, x1, g_ff, m3, r3, dx2, p, g_out, m2, r2, dg_ff, dg_out)
-    if rotary is None or row == 0:
-        q, kv = qkv
-        d_out = sg.wgrad(dp, o, D, inner, B, w_out) if need_w[1] else None
-        doc = ops.gemm(dp, w_out, B, inner, D, b_kmajor=True)
-        dq, dkv = ops.attention_pool_bwd(q, kv.view(B, n, 2 * inner), mask, o, doc, lse, heads, scale, hs, row + 1 if causal else None)
-        if rotary is not None:
-            ops.rotary_(dkv.view(M, 2 * inner), n, rotary, inverse=True, head_dim=hs)      # the saved kv is the rotated one; R^T maps its gradient back
-        # d h = dkv W_kv on every row, + dq W_q on the pooled rows (added with the skip gradient below)
-        dh = ops.gemm(dkv.view(M, 2 * inner), w_qkv[inner:], M, D, 2 * inner, b_kmajor=True)
-        dhq = ops.gemm(dq, w_qkv[:inner], B, D, inner, b_kmajor=True)
-        hr = _pool_view(dh, B, n, row)
-        t = torch.empty(B, D, dtype=dh.dtype, device=dh.device)
-        ops.copy_rows(hr, t)
-        ops.copy_rows(ops.add_rows(t, dhq), hr)
+    spec, B, n, inner = c.spec, c.B, c.n, c.spec.inner
+    M, D = t.x.shape
+    dx1, dp, d_ff1, d_ff2 = _ffn_backward(dx2, t, W, need, dg, c, sg, 0)
+    if spec.rotary is None or row == 0:
+        q, kv = t.qkv
+        d_out = sg.wgrad(dp, t.o, D, inner, B, W.w_out) if need.w_out else None
+        doc = ops.gemm(dp, W.w_out, B, inner, D, b_kmajor=True)
+        dq, dkv = ops.attention_pool_bwd(q, kv.view(B, n, 2 * inner), c.mask, t.o, doc, t.lse, spec.heads, spec.scale, spec.head_slot, row + 1 if spec.causal else None)
+        if spec.rotary is not None:
+            ops.rotary_(dkv.view(M, 2 * inner), n, spec.rotary, inverse=True, head_dim=spec.head_slot)    # the saved kv is the rotated one; R^T maps its gradient back
+        # d h = dkv W_kv on every row, + dq W_q on the pooled rows
+        dh = ops.gemm(dkv.view(M, 2 * inner), W.w_qkv[inner:], M, D, 2 * inner, b_kmajor=True)
+        _add_to_pooled_rows(dh, ops.gemm(dq, W.w_qkv[:inner], B, D, inner, b_kmajor=True), B, n, row)
         d_qkv = None
-        if need_w[0]:                                          # both parts of the weight gradient into ONE tensor (a bucket slice, if claimed)
-            d_qkv = _grad_out(w_qkv, (3 * inner, D), dp.dtype, dp.device)
-            sg.wgrad_into(dq, _pool_view(h, B, n, row), inner, D, B, d_qkv[:inner])
-            sg.wgrad_into(dkv.view(M, 2 * inner), h, 2 * inner, D, M, d_qkv[inner:])
+        if need.w_qkv:                                         # both parts of the weight gradient into ONE tensor (a bucket slice, if claimed)
+            d_qkv = _grad_out(W.w_qkv, (3 * inner, D), dp.dtype, dp.device)
+            sg.wgrad_into(dq, _pool_view(t.h, B, n, row), inner, D, B, d_qkv[:inner])
+            sg.wgrad_into(dkv.view(M, 2 * inner), t.h, 2 * inner, D, M, d_qkv[inner:])
         del dkv
     else:
-        oc = _pool_view(o.view(M, inner), B, n, row)
-        d_out = sg.wgrad(dp, oc, D, inner, B, w_out) if need_w[1] else None
+        d_out = sg.wgrad(dp, _pool_view(t.o.view(M, inner), B, n, row), D, inner, B, W.w_out) if need.w_out else None
         # the attention sees a gradient on the pooled query rows only (dK / dV of every row come from those queries)
         do = torch.zeros(M, inner, dtype=dp.dtype, device=dp.device)
-        ops.gemm(dp, w_out, B, inner, D, b_kmajor=True, out=_pool_view(do, B, n, row))
-        dqkv = ops.attention_bwd(qkv.view(B, n, 3 * inner), mask, o, do.view(B, n, inner), lse, heads, scale, causal, hs, 0.0, 0)
+        ops.gemm(dp, W.w_out, B, inner, D, b_kmajor=True, out=_pool_view(do, B, n, row))
+        dqkv = _attn_backward(do, t, c, 0)
         del do
-        ops.rotary_(dqkv.view(M, 3 * inner), n, rotary, inverse=True, head_dim=hs)
-        dh = ops.gemm(dqkv.view(M, 3 * inner), w_qkv, M, D, 3 * inner, b_kmajor=True)
-        d_qkv = sg.wgrad(dqkv.view(M, 3 * inner), h, 3 * inner, D, M, w_qkv) if need_w[0] else None
+        dh, d_qkv = _qkv_backward(dqkv, t, W, need, c, sg)
         del dqkv
-    dx, _ = ops.layernorm_bwd(dh, x, g_attn, m1, r1, dg=dg_attn)
-    # the skip connection carries a gradient on the pooled rows only
-    dxr = _pool_view(dx, B, n, row)
-    t = torch.empty(B, D, dtype=dx.dtype, device=dx.device)
-    ops.copy_rows(dxr, t)
-    ops.copy_rows(ops.add_rows(t, dx1), dxr)
-    return dx, [d_qkv, d_out, d_ff1, d_ff2]
+    dx, _ = ops.layernorm_bwd(dh, t.x, W.g_attn, t.m1, t.r1, dg=dg.g_attn)
+    _add_to_pooled_rows(dx, dx1, B, n, row)                    # the skip connection carries a gradient on the pooled rows only
+    return dx, dict(w_qkv=d_qkv, w_out=d_out, w_ff1=d_ff1, w_ff2=d_ff2)
 
 
 # ---- the whole stack: norm_in -> depth x (attention, feed-forward) -> norm_out ------------------------------------------
@@ -357,86 +380,62 @@ def stack_forward(x0: Tensor, B: int, n: int, spec: StackSpec, params: Sequence[
     pool_row = r: only token row r of every sample is wanted -> [B, D] (the last layer's row-wise part runs on those rows alone)"""
     assert len(params) == 2 + LAYER_PARAMS * spec.depth
     assert pool_row is None or (can_pool(spec) and out is None and 0 <= pool_row < n)
-    g_in, g_out = params[0], params[-1]
-    x, m_in, r_in = ops.layernorm_fwd(x0, g_in)
-    layers = []
+    x, m_in, r_in = ops.layernorm_fwd(x0, params[0])
     # dropout: one 64-bit seed per pass from torch's CPU generator (no device sync; torch.manual_seed makes it reproducible); layer l
     # uses seed + 2 l (attention) and seed + 2 l + 1 (feed-forward); the backward and a checkpointed re-run regenerate the same masks
     seed0 = _draw_seed() if (spec.attn_dropout > 0.0 or spec.ff_dropout > 0.0) else 0
+    layers, c = [], _Pass(spec, B, n, mask)
     for l in range(spec.depth):
-        W = params[1 + LAYER_PARAMS * l: 1 + LAYER_PARAMS * (l + 1)]
+        W, _ = layer_weights(params, l)
         if pool_row is not None and l == spec.depth - 1:
-            x_next, saved = _layer_forward_pooled(x, B, n, W, spec.heads, mask, spec.rotary, spec.causal, spec.dim_head ** -0.5, spec.head_slot, pool_row)
+            x, lt = _layer_forward_pooled(x, W, c, pool_row)
         else:
-            x_next, saved = _layer_forward(x, B, n, W, spec.heads, mask, spec.rotary, spec.causal, spec.dim_head ** -0.5, spec.head_slot,
-                                           (spec.attn_dropout, spec.ff_dropout, seed0 + 2 * l))
+            x, lt = _layer_forward(x, W, c, seed0 + 2 * l)
         if keep_tape:
-            layers.append((saved[0],) if spec.checkpoint else saved)
-        x = x_next
-    y, m_out, r_out = ops.layernorm_fwd(x, g_out, out=out, out_group=out_group)
-    tape = (x0, m_in, r_in, layers, x, m_out, r_out, seed0, pool_row) if keep_tape else None
-    return y, tape
+            layers.append(lt.x if spec.checkpoint else lt)       # checkpointing: the layer's input alone
+    y, m_out, r_out = ops.layernorm_fwd(x, params[-1], out=out, out_group=out_group)
+    return y, (x0, m_in, r_in, layers, x, m_out, r_out, seed0, pool_row) if keep_tape else None
 
 
-def stack_backward(dy: Tensor, tape, B: int, n: int, spec: StackSpec, params: Sequence[Tensor], mask: Optional[Tensor],
-                   need: Sequence[bool]):
+def stack_backward(dy: Tensor, tape, B: int, n: int, spec: StackSpec, params: Sequence[Tensor], mask: Optional[Tensor], need: Sequence[bool]):
     """dy [B*n, D] contiguous ([B, D] for a pooled forward) -> (dx0, grads aligned with `params` (None where not needed))"""
     x0, m_in, r_in, layers, x_last, m_out, r_out, seed0, pool_row = tape
-    gains = [params[0]] + [params[1 + LAYER_PARAMS * l + k] for l in range(spec.depth) for k in (0, 3, 4, 6)] + [params[-1]]
-    gg = _GainGrads(gains)
+    gg = _GainGrads(params, (True,) + spec.depth * IS_GAIN + (True,))
     grads: List[Optional[Tensor]] = [None] * len(params)
-    sg = _SideGemm(dy.device)
+    sg, c = _SideGemm(dy.device), _Pass(spec, B, n, mask)
     def stats_for(l: int):
-        """the row constants of layer l's fused feed-forward backward can be written by the kernel that produces its output gradient -- the
-        LayerNorm backward of the layer above it, or of norm_out -- whose input row is layer l's output (round 6: one pass over dOut, x2, x1
-        per layer less).  Not with recompute (layer l's tape does not exist yet at that point), dropout, a pooled layer (l itself, or the one
-        above it: its kernel's dx is completed on the pooled rows afterwards) or shapes the fused kernel does not take"""
-        if l < 0 or l >= spec.depth or spec.checkpoint or spec.ff_dropout != 0.0 or layers[l] is None:
+        """the row constants of layer l's fused feed-forward backward can be written by the kernel that produces its output gradient -- the LayerNorm
+        backward of the layer above it, or of norm_out -- whose input row is layer l's output.  Not with recompute (layer l's tape does not exist yet at that
+        point), dropout, a pooled layer (l itself, or the one above it: its kernel's dx is completed on the pooled rows afterwards) or shapes the fused kernel does not take"""
+        lt = layers[l] if 0 <= l < spec.depth else None
+        if not isinstance(lt, LayerTape) or spec.ff_dropout != 0.0 or (pool_row is not None and l >= spec.depth - 2):
             return None
-        if pool_row is not None and l >= spec.depth - 2:
-            return None
-        sv = layers[l]
-        if len(sv) < 18:
-            return None
-        Wl = params[1 + LAYER_PARAMS * l: 1 + LAYER_PARAMS * (l + 1)]
-        return ops.ffn_stats_request(Wl[7], Wl[6], sv[10], sv[16], sv[17])
+        Wl, _ = layer_weights(params, l)
+        return ops.ffn_stats_request(Wl.w_ff2, Wl.g_inner, lt.x1, lt.m4, lt.r4)
 
     st = stats_for(spec.depth - 1) if pool_row is None else None
     dx, _ = ops.layernorm_bwd(dy, x_last, params[-1], m_out, r_out, dg=gg.views[-1], ffn_stats=st)
     x_out = x_last if pool_row is None else None             # the output of the layer being walked (= the saved input of the one above it)
     for l in reversed(range(spec.depth)):
-        base = 1 + LAYER_PARAMS * l
-        W = params[base: base + LAYER_PARAMS]
-        saved = layers[l]
+        W, base = layer_weights(params, l)
+        lt, seed = layers[l], seed0 + 2 * l
         pooled = pool_row is not None and l == spec.depth - 1
-        if spec.checkpoint:                      # re-run the layer forward from its saved input
-            if pooled:
-                _, saved = _layer_forward_pooled(saved[0], B, n, W, spec.heads, mask, spec.rotary, spec.causal, spec.dim_head ** -0.5, spec.head_slot, pool_row)
-            else:
-                _, saved = _layer_forward(saved[0], B, n, W, spec.heads, mask, spec.rotary, spec.causal, spec.dim_head ** -0.5, spec.head_slot,
-                                          (spec.attn_dropout, spec.ff_dropout, seed0 + 2 * l))
-        need_w = [need[base + 1], need[base + 2], need[base + 5], need[base + 7]]
+        if not isinstance(lt, LayerTape):        # checkpointed: re-run the layer forward from its saved input
+            _, lt = _layer_forward_pooled(lt, W, c, pool_row) if pooled else _layer_forward(lt, W, c, seed)
+        (need_l, _), (dg, _) = layer_weights(need, l), layer_weights(gg.views, l)
+        below = stats_for(l - 1)                 # (None for the layer under a pooled one)
         if pooled:
-            dx, dws = _layer_backward_pooled(dx, saved, B, n, W, spec.heads, mask, gg.views[1 + 4 * l: 5 + 4 * l], need_w, sg, spec.rotary, spec.causal,
-                                             spec.dim_head ** -0.5, spec.head_slot, pool_row)
-            st = None
+            dx, dws = _layer_backward_pooled(dx, lt, W, need_l, dg, c, sg, pool_row)
         else:
-            below = stats_for(l - 1)
-            dx, dws = _layer_backward(dx, saved, B, n, W, spec.heads, mask, gg.views[1 + 4 * l: 5 + 4 * l], need_w, sg, spec.rotary, spec.causal, spec.dim_head ** -0.5, spec.head_slot,
-                                      (spec.attn_dropout, spec.ff_dropout, seed0 + 2 * l), x2=x_out, rowc=None if st is None else st[5], below=below)
-            st = below
-        x_out = saved[0]
-        layers[l] = None                         # release this layer's activations
+            dx, dws = _layer_backward(dx, lt, W, need_l, dg, c, sg, seed, x_out, (None if st is None else st[5], below))
+        st = below
+        x_out, layers[l] = lt.x, None            # release this layer's activations
         sg.layer_done()
-        grads[base + 1], grads[base + 2], grads[base + 5], grads[base + 7] = dws
+        for f, d in dws.items():
+            grads[base + LayerWeights._fields.index(f)] = d
     dx0, _ = ops.layernorm_bwd(dx, x0, params[0], m_in, r_in, dg=gg.views[0])
     sg.join()
-    gfin = gg.finish()
-    grads[0], grads[-1] = gfin[0], gfin[-1]
-    for l in range(spec.depth):
-        base = 1 + LAYER_PARAMS * l
-        for j, k in enumerate((0, 3, 4, 6)):
-            grads[base + k] = gfin[1 + 4 * l + j]
+    gg.finish(grads)
     return dx0, [g if nd else None for g, nd in zip(grads, need)]
 
 
