@@ -20,7 +20,7 @@ extern "C" {
 #endif
 
 enum { XCLIP_F32 = 0, XCLIP_BF16 = 1 };
-#define XCLIP_ABI_VERSION 28
+#define XCLIP_ABI_VERSION 29
 
 int xclip_abi_version(void);
 const char* xclip_last_error(void);
@@ -412,7 +412,7 @@ int xclip_neg_cosine_bwd(const void* p, const void* z, const float* cosv, const 
                          void* dp, int64_t rows, int64_t dim, int dtype, void* stream);
 
 /* ---- the optimizer step: clip by global norm + AdamW with fp32 master weights (x_clip_amd/optim.py FusedAdamW) ------------------------
- * The reference has no optimizer; these three replace torch.nn.utils.clip_grad_norm_ (gradnorm_partial + optim_prepare: without its read
+ * The reference has no optimizer; these replace torch.nn.utils.clip_grad_norm_ (gradnorm_partial + optim_prepare: without its read
  * of the norm on the host) and torch.optim.AdamW.step (adamw_step: one pass instead of a chain of foreach launches), for ALL parameters of
  * a model at once.  `table`: device array of 48-byte chunk records, one per piece of <= 65536 elements of a parameter
  * (csrc/kernels/optim.h OptChunk: parameter pointer, gradient pointer, element offset into the flat fp32 state arrays, count, dtypes,
@@ -428,13 +428,22 @@ int xclip_neg_cosine_bwd(const void* p, const void* z, const float* cosv, const 
  *     found_nonfinite the kernel returns at once; else g *= clip_coef; w *= 1 - lr wd; m = b1 m + (1 - b1) g; v = b2 v + (1 - b2) g^2;
  *     w -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps), t = step - step_base[parameter] (torch.optim.AdamW's order).
  *     bf16 parameters: w is master[state_off + i] (fp32) and the parameter is written as its round-to-nearest-even bf16; fp32
- *     parameters are w themselves and `master` may be NULL.  exp_avg / exp_avg_sq / master: the flat fp32 arrays, 16-byte aligned. */
+ *     parameters are w themselves and `master` may be NULL.  exp_avg / exp_avg_sq / master: the flat fp32 arrays, 16-byte aligned.
+ *   adamw_ema_step (ABI 29): adamw_step plus an exponential moving average of the weights in the same pass.  `ema`: one more flat fp32
+ *     array, indexed by state_off as exp_avg (for bf16 AND fp32 parameters), initialised by the caller to the weights.  Per element, after
+ *     the update above: ema += (1 - d_u) (w - ema) in fp32, w the fp32 master where there is one.  u = step of the state block (the applied
+ *     steps including this one, >= 1), d_u = ema_warmup ? min(ema_decay, (1 + u) / (10 + u)) : ema_decay, 0 <= ema_decay < 1; 1 - d_u is
+ *     formed in double and rounded once.  found_nonfinite: returns at once, ema keeps every bit; chunks that are not in the table are not
+ *     averaged.  m, v, w and the parameter get exactly adamw_step's bits. */
 int xclip_gradnorm_partial(const void* table, int64_t chunk0, int64_t count, int g_dtype, float* partials, void* stream);
 int xclip_optim_prepare(const float* partials, int64_t n_chunks, float max_norm, int clip, void* state_block, int32_t* step_base,
                         const int32_t* absent, int64_t n_absent, void* stream);
 int xclip_adamw_step(const void* table, int64_t chunk0, int64_t count, int p_dtype, int g_dtype, float* exp_avg, float* exp_avg_sq,
                      float* master, const void* state_block, int32_t* step_base, double lr, double beta1, double beta2, double eps,
                      double weight_decay, void* stream);
+int xclip_adamw_ema_step(const void* table, int64_t chunk0, int64_t count, int p_dtype, int g_dtype, float* exp_avg, float* exp_avg_sq,
+                         float* master, const void* state_block, int32_t* step_base, double lr, double beta1, double beta2, double eps,
+                         double weight_decay, float* ema, double ema_decay, int ema_warmup, void* stream);
 
 #ifdef __cplusplus
 }

@@ -4,7 +4,11 @@ random gradients.  HIP events around each step, the variants alternated inside e
 shader clock is sampled right behind the timed steps (xclip_clock_sample) and the LayerNorm-forward streaming figure of the same
 session is printed beside the fused step's achieved bytes / s.  The fused step is timed with two chunk sizes (elements per work-group: the
 product's 64 Ki and 16 Ki) alternated in the same rounds, and its three phases -- norm pass, the one-work-group prepare kernel, update pass -- are
-timed on their own (the phases of a step are dependent launches: their sum is the step without the gaps between them).
+timed on their own (the phases of a step are dependent launches: their sum is the step without the gaps between them).  The weight EMA
+(FusedAdamW(ema_decay=...)) is timed in the same rounds: its update pass (adamw_ema_kernel, 36 B per parameter) bracketed by two runs of
+the EMA-off pass (28 B; the ratio is taken against the mean of the two and printed beside the byte ratio 36 / 28 with 10 % margin), the
+whole step with EMA, and the two-pass alternative: the EMA-off step followed by torch._foreach_lerp_ on fp32 copies from the fp32
+masters (bf16) / parameters (fp32).
 usage: python tools/probe_optim.py [repeats]"""
 import os
 import sys
@@ -14,6 +18,8 @@ import torch
 from x_clip_amd import CLIP, FusedAdamW, _lib, ops
 
 MAX_NORM = 1.0
+EMA_DECAY = 0.9999
+EMA_EXPECTED = 36.0 / 28.0 * 1.1   # the EMA update pass over the EMA-off pass: its byte ratio, 10 % margin for a ninth address stream
 ALT_CHUNK = 16384           # the second chunk size the fused step is timed with (the product's: ops.OPTIM_CHUNK)
 
 
@@ -85,6 +91,24 @@ def main():
         variants["  phase: norm pass alone"] = norm_pass
         variants["  phase: prepare kernel alone"] = lambda: ops.optim_prepare(D.partials, D.n_chunks, MAX_NORM, D.block, D.step_base, D.absent, D.n_absent)
         variants["  phase: update pass alone"] = update_pass
+        ps_e = make()
+        fe = FusedAdamW(ps_e, lr=1e-4, max_grad_norm=MAX_NORM, ema_decay=EMA_DECAY)
+        fe.step()
+        E = fe._one()
+
+        def update_pass_ema():
+            for c0, cn, gi, pc, gc in E.segments:
+                grp = fe.param_groups[gi]
+                ops.adamw_ema_step(E.table, c0, cn, half[pc], half[gc], E.exp_avg, E.exp_avg_sq, E.master, E.block, E.step_base, grp["lr"],
+                                   grp["betas"][0], grp["betas"][1], grp["eps"], grp["weight_decay"], E.ema, fe.ema_decay, fe.ema_warmup)
+
+        variants["  phase: update pass alone, EMA on"] = update_pass_ema
+        variants["  phase: update pass alone (EMA off) again"] = update_pass     # (the order inside a round matters: EMA on is bracketed)
+        variants["Fused with EMA (ema_decay)"] = fe.step
+        weights = [fo.state[p]["master"] if dtype == torch.bfloat16 else p.detach() for p in ps]
+        lerp_ema = [w.clone() for w in weights]                  # the two-pass alternative's fp32 EMA, one tensor per parameter
+        variants["  _foreach_lerp_ on the fp32 weights alone"] = lambda: torch._foreach_lerp_(lerp_ema, weights, 1.0 - EMA_DECAY)
+        variants["Fused (EMA off) + _foreach_lerp_"] = lambda: (fo.step(), torch._foreach_lerp_(lerp_ema, weights, 1.0 - EMA_DECAY))
         ps_f = make()
         to = torch.optim.AdamW(ps_f, lr=1e-4, foreach=True)
         variants["clip_grad_norm_ + AdamW(foreach)"] = lambda ps_f=ps_f, to=to: (torch.nn.utils.clip_grad_norm_(ps_f, MAX_NORM), to.step())
@@ -114,11 +138,18 @@ def main():
             extra = f"   {n * bytes_per / med / 1e6:5.2f} TB/s of {bytes_per} B / parameter" if k.startswith("Fused") else ""
             if "norm pass" in k:
                 extra = f"   {n * (bytes_per - 28) / med / 1e6:5.2f} TB/s of {bytes_per - 28} B / parameter"
-            if "update pass" in k:
+            if "EMA on" in k:
+                extra = f"   {n * 36 / med / 1e6:5.2f} TB/s of 36 B / parameter"
+            elif "update pass" in k:
                 extra = f"   {n * (bytes_per - (2 if dtype == torch.bfloat16 else 4)) / med / 1e6:5.2f} TB/s of {bytes_per - (2 if dtype == torch.bfloat16 else 4)} B / parameter"
             print(f"  {k:44s} median {med:8.1f} us   best {ts[0]:8.1f} us{extra}")
+        med = {k: sorted(ts)[len(ts) // 2] for k, ts in times.items()}
+        off = 0.5 * (med["  phase: update pass alone"] + med["  phase: update pass alone (EMA off) again"])
+        ratio = med["  phase: update pass alone, EMA on"] / off
+        print(f"  EMA update pass / EMA-off update pass (mean of the two around it): {ratio:.3f} (expected <= {EMA_EXPECTED:.3f}: {'met' if ratio <= EMA_EXPECTED else 'NOT met'}); "
+              f"step with EMA / step + _foreach_lerp_: {med['Fused with EMA (ema_decay)'] / med['Fused (EMA off) + _foreach_lerp_']:.3f}")
         print(f"  work-groups per step: {D.n_chunks} with {product_chunk}-element chunks, {fc._one().n_chunks} with {ALT_CHUNK}")
-        del ps, ps_f, ps_c, fo, fc, to, variants, D
+        del ps, ps_f, ps_c, ps_e, fo, fc, fe, to, variants, D, E, weights, lerp_ema
         torch.cuda.empty_cache()
 
 

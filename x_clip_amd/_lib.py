@@ -104,9 +104,10 @@ _SIGNATURES = {
     "xclip_gradnorm_partial": (c_int, [P, L, L, I, P, P]),
     "xclip_optim_prepare": (c_int, [P, L, F, I, P, P, P, L, P]),
     "xclip_adamw_step": (c_int, [P, L, L, I, I, P, P, P, P, P, D, D, D, D, D, P]),
+    "xclip_adamw_ema_step": (c_int, [P, L, L, I, I, P, P, P, P, P, D, D, D, D, D, P, D, I, P]),
 }
 EXPORTS = tuple(_SIGNATURES)
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 
 def _bind(path: str):

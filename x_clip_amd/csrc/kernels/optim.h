@@ -10,6 +10,7 @@
 //                             (OptBlock): the norm, the clip factor, the non-finite flag, the step counter.  Nothing goes to the host.
 //   adamw_kernel              one work-group per chunk: returns at once when the gradients were not finite (the step is skipped ON THE
 //                             DEVICE); otherwise one streaming pass, fp32 arithmetic, in torch.optim.AdamW's operation order.
+//   adamw_ema_kernel          the same pass with a weight EMA kept beside the moments (FusedAdamW(ema_decay=...)): + 8 bytes per parameter.
 //
 // Algorithmic HBM traffic per parameter: bf16 2 (g, norm pass) + 2 (g) + 12 (m, v, master in) + 12 (out) + 2 (p out) = 30 bytes;
 // fp32 4 + 4 + 12 (m, v, p in) + 12 (out) = 32 bytes.  Everything is read once and written once: non-temporal hint, as in rows.h.
@@ -214,6 +215,73 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_kernel(const OptChunk* __re
         m[i] = mi;
         v[i] = vi;
         w[i] = wi;
+        if (MASTER) p[i] = from_f32<P>(wi);
+    }
+}
+
+// ---- the update with a weight EMA ----------------------------------------------------------------------------------------------------------
+// adamw_kernel's streaming pass with one more flat fp32 array, `ema` (laid out as exp_avg): after adamw_elem has produced the new w,
+// e += omd * (w - e) in fp32, on the fp32 master where there is one (an EMA of the rounded bf16 parameters stalls as bf16 AdamW does).
+// omd = 1 - d_u is formed once per work-group, in double, from the device block: u = blk.step, the applied steps including this one
+// (>= 1; a skipped step advances nothing), d_u = warmup ? min(decay, (1 + u) / (10 + u)) : decay.  A skipped step returns before it
+// reads anything; chunks of parameters without a gradient are not in the table: their ema keeps its bits, as the parameter does.
+XC_DEV void ema_elem(float w, float& e, float omd) { e += omd * (w - e); }
+
+template <typename P, typename G, bool MASTER>
+__global__ __launch_bounds__(OPT_THREADS) void adamw_ema_kernel(const OptChunk* __restrict__ table, int chunk0, float* __restrict__ exp_avg,
+                                                                float* __restrict__ exp_avg_sq, float* __restrict__ master,
+                                                                float* __restrict__ ema, const OptBlock* __restrict__ blk,
+                                                                int32_t* __restrict__ step_base, AdamWArgs a, double ema_decay, int ema_warmup) {
+    const OptBlock b = *blk;
+    if (b.found_nonfinite) return;                             // the step is skipped: the EMA too keeps every bit
+    const OptChunk c = table[chunk0 + (int)blockIdx.x];
+    if ((c.dtypes & 0xff) != OptDtype<P>::CODE || ((c.dtypes >> 8) & 0xff) != OptDtype<G>::CODE) return;
+    const int tid = threadIdx.x;
+    int base = step_base[c.param];                             // (the parameter's own step count: as adamw_kernel)
+    if (base < 0) {
+        base = b.step - 1;
+        if (tid == 0 && c.first) step_base[c.param] = base;
+    }
+    const int t = b.step - base;
+    const double bc1 = 1.0 - opt_ipow(a.beta1, t), bc2 = 1.0 - opt_ipow(a.beta2, t);
+    const float step_size = (float)(a.lr / bc1), bc2_sqrt = (float)sqrt(bc2), clip = b.clip_coef;
+    const double ramp = (1.0 + (double)b.step) / (10.0 + (double)b.step);
+    const float omd = (float)(1.0 - (ema_warmup && ramp < ema_decay ? ramp : ema_decay));
+
+    P* p = reinterpret_cast<P*>(c.p);
+    const G* g = reinterpret_cast<const G*>(c.g);
+    float* m = exp_avg + c.state_off;
+    float* v = exp_avg_sq + c.state_off;
+    float* e = ema + c.state_off;
+    float* w = MASTER ? master + c.state_off : reinterpret_cast<float*>(c.p);
+    const int nvec = (opt_aligned16(c.p) && opt_aligned16(c.g) && (c.state_off & 3) == 0) ? c.n / 8 : 0;
+    for (int i = tid; i < nvec; i += OPT_THREADS) {
+        const long o = (long)i * 8;
+        float gv[8], mv[8], vv[8], wv[8], ev[8];
+        opt_load8<true>(g + o, gv);
+        opt_load8<true>(m + o, mv);
+        opt_load8<true>(v + o, vv);
+        opt_load8<true>(w + o, wv);
+        opt_load8<true>(e + o, ev);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            adamw_elem(gv[j], wv[j], mv[j], vv[j], a, clip, step_size, bc2_sqrt);
+            ema_elem(wv[j], ev[j], omd);
+        }
+        opt_store8<true>(m + o, mv);
+        opt_store8<true>(v + o, vv);
+        opt_store8<true>(w + o, wv);
+        opt_store8<true>(e + o, ev);
+        if (MASTER) opt_store8<true>(p + o, wv);               // (rounds to the parameter's storage type)
+    }
+    for (int i = nvec * 8 + tid; i < c.n; i += OPT_THREADS) {  // scalar tail / unaligned chunk
+        float wi = w[i], mi = m[i], vi = v[i], ei = e[i];
+        adamw_elem(to_f32(g[i]), wi, mi, vi, a, clip, step_size, bc2_sqrt);
+        ema_elem(wi, ei, omd);
+        m[i] = mi;
+        v[i] = vi;
+        w[i] = wi;
+        e[i] = ei;
         if (MASTER) p[i] = from_f32<P>(wi);
     }
 }

@@ -1809,6 +1809,16 @@ int xclip_optim_prepare(const float* partials, int64_t n_chunks, float max_norm,
     return check_launch(__func__);
 }
 
+static AdamWArgs adamw_args(double lr, double beta1, double beta2, double eps, double weight_decay) {
+    AdamWArgs a;
+    a.decay = (float)(1.0 - lr * weight_decay);
+    a.b1 = (float)beta1; a.omb1 = (float)(1.0 - beta1);
+    a.b2 = (float)beta2; a.omb2 = (float)(1.0 - beta2);
+    a.eps = (float)eps;
+    a.lr = lr; a.beta1 = beta1; a.beta2 = beta2;
+    return a;
+}
+
 int xclip_adamw_step(const void* table, int64_t chunk0, int64_t count, int p_dtype, int g_dtype, float* exp_avg, float* exp_avg_sq,
                      float* master, const void* state_block, int32_t* step_base, double lr, double beta1, double beta2, double eps,
                      double weight_decay, void* stream) {
@@ -1820,18 +1830,35 @@ int xclip_adamw_step(const void* table, int64_t chunk0, int64_t count, int p_dty
     XC_REQUIRE(table && exp_avg && exp_avg_sq && state_block && step_base && aligned16(table) && aligned16(exp_avg) && aligned16(exp_avg_sq),
                "null or misaligned pointer");
     XC_REQUIRE(p_dtype == XCLIP_F32 || (master && aligned16(master)), "bf16 parameters need the fp32 master array");
-    AdamWArgs a;
-    a.decay = (float)(1.0 - lr * weight_decay);
-    a.b1 = (float)beta1; a.omb1 = (float)(1.0 - beta1);
-    a.b2 = (float)beta2; a.omb2 = (float)(1.0 - beta2);
-    a.eps = (float)eps;
-    a.lr = lr; a.beta1 = beta1; a.beta2 = beta2;
+    const AdamWArgs a = adamw_args(lr, beta1, beta2, eps, weight_decay);
     dim3 grid((unsigned)count), block(OPT_THREADS);
     hipStream_t st = (hipStream_t)stream;
 #define XC_ADAMW(P, G, M) hipLaunchKernelGGL((adamw_kernel<P, G, M>), grid, block, 0, st, (const OptChunk*)table, (int)chunk0, exp_avg, exp_avg_sq, master, (const OptBlock*)state_block, step_base, a)
     if (p_dtype == XCLIP_BF16) { if (g_dtype == XCLIP_BF16) XC_ADAMW(bf16_t, bf16_t, true); else XC_ADAMW(bf16_t, float, true); }
     else                       { if (g_dtype == XCLIP_BF16) XC_ADAMW(float, bf16_t, false); else XC_ADAMW(float, float, false); }
 #undef XC_ADAMW
+    return check_launch(__func__);
+}
+
+int xclip_adamw_ema_step(const void* table, int64_t chunk0, int64_t count, int p_dtype, int g_dtype, float* exp_avg, float* exp_avg_sq,
+                         float* master, const void* state_block, int32_t* step_base, double lr, double beta1, double beta2, double eps,
+                         double weight_decay, float* ema, double ema_decay, int ema_warmup, void* stream) {
+    XC_REQUIRE(dtype_ok(p_dtype) && dtype_ok(g_dtype), "bad dtype");
+    XC_REQUIRE(chunk0 >= 0 && count >= 0 && chunk0 + count < (1ll << 31), "bad chunk range");
+    XC_REQUIRE(lr >= 0.0 && lr < 1e30 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0 && eps < 1e30 &&
+               weight_decay >= 0.0 && weight_decay < 1e30, "bad hyper-parameter");
+    XC_REQUIRE(ema_decay >= 0.0 && ema_decay < 1.0, "ema_decay must be in [0, 1)");
+    if (count == 0) return 0;
+    XC_REQUIRE(table && exp_avg && exp_avg_sq && ema && state_block && step_base && aligned16(table) && aligned16(exp_avg) &&
+               aligned16(exp_avg_sq) && aligned16(ema), "null or misaligned pointer");
+    XC_REQUIRE(p_dtype == XCLIP_F32 || (master && aligned16(master)), "bf16 parameters need the fp32 master array");
+    const AdamWArgs a = adamw_args(lr, beta1, beta2, eps, weight_decay);
+    dim3 grid((unsigned)count), block(OPT_THREADS);
+    hipStream_t st = (hipStream_t)stream;
+#define XC_ADAMW_EMA(P, G, M) hipLaunchKernelGGL((adamw_ema_kernel<P, G, M>), grid, block, 0, st, (const OptChunk*)table, (int)chunk0, exp_avg, exp_avg_sq, master, ema, (const OptBlock*)state_block, step_base, a, ema_decay, ema_warmup ? 1 : 0)
+    if (p_dtype == XCLIP_BF16) { if (g_dtype == XCLIP_BF16) XC_ADAMW_EMA(bf16_t, bf16_t, true); else XC_ADAMW_EMA(bf16_t, float, true); }
+    else                       { if (g_dtype == XCLIP_BF16) XC_ADAMW_EMA(float, bf16_t, false); else XC_ADAMW_EMA(float, float, false); }
+#undef XC_ADAMW_EMA
     return check_launch(__func__);
 }
 

@@ -1398,3 +1398,18 @@ def adamw_step(table: Tensor, chunk0: int, count: int, param_dtype, grad_dtype, 
     _lib.check(_lib.lib().xclip_adamw_step(table.data_ptr(), chunk0, count, _DTYPES[param_dtype], _DTYPES[grad_dtype], exp_avg.data_ptr(),
                                            exp_avg_sq.data_ptr(), _ptr(master), block.data_ptr(), step_base.data_ptr(), float(lr), float(beta1),
                                            float(beta2), float(eps), float(weight_decay), _stream(table)), "xclip_adamw_step")
+
+
+def adamw_ema_step(table: Tensor, chunk0: int, count: int, param_dtype, grad_dtype, exp_avg: Tensor, exp_avg_sq: Tensor, master: Optional[Tensor],
+                   block: Tensor, step_base: Tensor, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float, ema: Tensor,
+                   ema_decay: float, ema_warmup: bool) -> None:
+    """`adamw_step` with the weight EMA in the same pass: ema += (1 - d)(w - ema) in fp32 on the updated (master) weight, d = `ema_decay`,
+    or min(ema_decay, (1 + u) / (10 + u)) with `ema_warmup` (u: the applied steps in `block`); a skipped step leaves `ema` alone"""
+    _dev_check(table, exp_avg, exp_avg_sq, master, block, step_base, ema)
+    assert table.dtype == torch.uint8 and table.numel() >= (chunk0 + count) * OPTIM_CHUNK_BYTES
+    assert exp_avg.dtype == torch.float32 and exp_avg_sq.dtype == torch.float32 and (master is None or master.dtype == torch.float32)
+    assert ema.dtype == torch.float32 and ema.numel() == exp_avg.numel()
+    _lib.check(_lib.lib().xclip_adamw_ema_step(table.data_ptr(), chunk0, count, _DTYPES[param_dtype], _DTYPES[grad_dtype], exp_avg.data_ptr(),
+                                               exp_avg_sq.data_ptr(), _ptr(master), block.data_ptr(), step_base.data_ptr(), float(lr),
+                                               float(beta1), float(beta2), float(eps), float(weight_decay), ema.data_ptr(), float(ema_decay),
+                                               int(bool(ema_warmup)), _stream(table)), "xclip_adamw_ema_step")

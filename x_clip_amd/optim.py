@@ -8,9 +8,11 @@ Why: `torch.optim.AdamW` on a `.bfloat16()` model keeps both moments in bf16 and
 learning rates most updates are below half an ulp of the weight and are rounded away.  Here the model keeps exactly the bf16 tensors it
 has (forward and backward are untouched); the optimizer owns an fp32 copy, updates that, and writes each parameter as its rounded value.
 Python does bookkeeping only: every number is computed by the HIP kernels, nothing is read back to the host during a step.
+`ema_decay=...` keeps an fp32 moving average of those unrounded weights in the same pass; `with opt.ema_weights():` evaluates on it.
 """
 from __future__ import annotations
 
+from contextlib import contextmanager
 from itertools import chain
 from typing import Optional
 
@@ -33,7 +35,7 @@ _BLK_NORM, _BLK_CLIP, _BLK_BAD, _BLK_STEP, _BLK_SKIPPED = 0, 1, 2, 3, 4
 class _DeviceState:
     """flat state, chunk table and state block of the parameters that live on one device"""
 
-    def __init__(self, device, params):
+    def __init__(self, device, params, ema=False):
         self.device = device
         # bf16 parameters first: the master array covers only them
         self.params = [pg for pg in params if pg[0].dtype == torch.bfloat16] + [pg for pg in params if pg[0].dtype != torch.bfloat16]
@@ -46,6 +48,7 @@ class _DeviceState:
         self.exp_avg = torch.zeros(max(off, 1), dtype=torch.float32, device=device)
         self.exp_avg_sq = torch.zeros(max(off, 1), dtype=torch.float32, device=device)
         self.master = torch.zeros(master_len, dtype=torch.float32, device=device) if master_len else None
+        self.ema = torch.zeros(max(off, 1), dtype=torch.float32, device=device) if ema else None      # (every parameter, fp32 ones too)
         self.block = torch.zeros(ops.OPTIM_BLOCK_WORDS, dtype=torch.int32, device=device)
         self.step_base = torch.full((max(len(self.params), 1),), -1, dtype=torch.int32, device=device)
         self.max_chunks = sum((p.numel() + ops.OPTIM_CHUNK - 1) // ops.OPTIM_CHUNK for p, _ in self.params)
@@ -89,6 +92,13 @@ class FusedAdamW(torch.optim.Optimizer):
       out fresh gradient addresses every step: then every step rebuilds (host time) and uploads, through a ring of 4 pinned staging
       buffers -- the host waits only if it runs more than 4 rebuilt steps ahead of the device: that bounds the queue, it does not drain it.
     * parameters whose `.grad` is None are left alone and their own step count does not advance (torch semantics).
+    * `ema_decay` (None: off -- no array, the launches and bits of an optimizer without the keyword): an exponential moving average of the
+      weights, fp32, 4 bytes per parameter, updated INSIDE the update pass: ema += (1 - d)(w - ema) on the fp32 master (bf16 parameters) or
+      the parameter (fp32) right after its update.  It is kept here because only the optimizer has what it needs: the unrounded weights (at
+      d = 0.999 an EMA of the bf16 parameters moves by less than half an ulp per step and stalls), the skip decision (a skipped step leaves
+      the EMA bit-identical) and the applied step count u behind `ema_warmup` (d = min(ema_decay, (1 + u) / (10 + u)), timm's ramp).
+      Initialised to the weights (exact); parameters without a gradient are not averaged.  `state[p]["ema"]` is a view of the flat array;
+      `with opt.ema_weights():` evaluates or checkpoints the model on the averaged weights.
 
     Streams: `step()` runs on the current stream.  The backward's side streams join the current stream before `backward()` returns; with
     `GradSync` call `sync.finish()` FIRST (it orders the current stream behind the all-reduces).  Distributed training needs nothing else:
@@ -100,7 +110,7 @@ class FusedAdamW(torch.optim.Optimizer):
     persistent slice only while `.grad` is None, and the re-created `.grad` has the same address, so the table stays valid."""
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
-                 max_grad_norm: Optional[float] = None):
+                 max_grad_norm: Optional[float] = None, ema_decay: Optional[float] = None, ema_warmup: bool = True):
         if not 0.0 <= lr:
             raise ValueError(f"invalid learning rate: {lr}")
         if not 0.0 <= eps:
@@ -111,6 +121,11 @@ class FusedAdamW(torch.optim.Optimizer):
             raise ValueError(f"invalid weight_decay: {weight_decay}")
         if max_grad_norm is not None and not max_grad_norm > 0.0:
             raise ValueError(f"invalid max_grad_norm: {max_grad_norm}")
+        if ema_decay is not None and not 0.0 <= ema_decay < 1.0:
+            raise ValueError(f"invalid ema_decay: {ema_decay}")
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self._ema_swapped = False                               # inside `with ema_weights():`
         self._devs = None
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.max_grad_norm = max_grad_norm
@@ -134,7 +149,7 @@ class FusedAdamW(torch.optim.Optimizer):
                 ops._dev_check(p)
                 if p.numel():
                     by_dev.setdefault(p.device, []).append((p, gi))
-        self._devs = {dev: _DeviceState(dev, ps) for dev, ps in by_dev.items()}
+        self._devs = {dev: _DeviceState(dev, ps, self.ema_decay is not None) for dev, ps in by_dev.items()}
         self._where = {}                                        # id(param) -> (device state, index)
         with torch.no_grad():
             for D in self._devs.values():
@@ -145,6 +160,9 @@ class FusedAdamW(torch.optim.Optimizer):
                     if p.dtype == torch.bfloat16:
                         st["master"] = D.view(D.master, i)
                         st["master"].copy_(p)                   # bf16 -> fp32: exact
+                    if D.ema is not None:
+                        st["ema"] = D.view(D.ema, i)
+                        st["ema"].copy_(p)                      # (= the master of a bf16 parameter)
 
     def _one(self) -> _DeviceState:
         if len(self._devs) != 1:
@@ -214,6 +232,8 @@ class FusedAdamW(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
+        if self._ema_swapped:
+            raise RuntimeError("x_clip_amd FusedAdamW: step() inside `with ema_weights():` -- the parameters hold the averaged weights")
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -236,14 +256,52 @@ class FusedAdamW(torch.optim.Optimizer):
                 ops.optim_prepare(D.partials, D.n_chunks, self.max_grad_norm, D.block, D.step_base, D.absent, D.n_absent)
                 for c0, n, gi, pc, gc in D.segments:
                     g = self.param_groups[gi]
-                    ops.adamw_step(D.table, c0, n, dt[pc], dt[gc], D.exp_avg, D.exp_avg_sq, D.master, D.block, D.step_base,
-                                   g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"])
+                    if D.ema is None:
+                        ops.adamw_step(D.table, c0, n, dt[pc], dt[gc], D.exp_avg, D.exp_avg_sq, D.master, D.block, D.step_base,
+                                       g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"])
+                    else:
+                        ops.adamw_ema_step(D.table, c0, n, dt[pc], dt[gc], D.exp_avg, D.exp_avg_sq, D.master, D.block, D.step_base,
+                                           g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], D.ema, self.ema_decay,
+                                           self.ema_warmup)
         return loss
+
+    # ---- the averaged weights ----
+    @contextmanager
+    def ema_weights(self):
+        """`with opt.ema_weights(): clip.eval(); ...; torch.save(clip.state_dict(), path)`: inside, every parameter holds its EMA (bf16
+        parameters its round-to-nearest-even bf16; parameters never stepped hold their initial value, which is their EMA); on exit bf16
+        parameters are rewritten from their masters (exact: a parameter always is its rounded master) and fp32 parameters from a stash
+        taken on entry, so training goes on with the bits it had.  Plain copies on the current stream, in place: addresses do not change and
+        the chunk table stays valid.  `step()` inside raises."""
+        if self.ema_decay is None:
+            raise RuntimeError("x_clip_amd FusedAdamW: ema_weights() needs an optimizer built with ema_decay")
+        if self._ema_swapped:
+            raise RuntimeError("x_clip_amd FusedAdamW: ema_weights() is already active")
+        stash = []
+        with torch.no_grad():
+            for D in self._devs.values():
+                for i, (p, _) in enumerate(D.params):
+                    if p.dtype != torch.bfloat16:
+                        stash.append((p, p.detach().clone()))
+                    p.copy_(D.view(D.ema, i))
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            with torch.no_grad():
+                for D in self._devs.values():
+                    for i, (p, _) in enumerate(D.params):
+                        if p.dtype == torch.bfloat16:
+                            p.copy_(D.view(D.master, i))
+                for p, saved in stash:
+                    p.copy_(saved)
+            self._ema_swapped = False
 
     # ---- checkpoints ----
     def state_dict(self):
         """`torch.optim.AdamW`'s layout (`step`, `exp_avg`, `exp_avg_sq` per parameter that has been stepped, fp32) plus `master` for bf16
-        parameters and, beside torch's two keys, `max_grad_norm` and `skipped_steps` (per device).  Copies (not views of the flat state);
+        parameters, `ema` with `ema_decay` and, beside torch's two keys, `max_grad_norm`, `skipped_steps` (per device) and -- with `ema_decay`
+        only: a dict of an optimizer without it is what it was -- `ema_decay` / `ema_warmup`.  Copies (not views of the flat state);
         reads the step counts back: a checkpoint is a synchronisation point.  `register_state_dict_pre_hook` / `_post_hook` hooks run."""
         for hook in self._optimizer_state_dict_pre_hooks.values():
             hook(self)
@@ -266,9 +324,13 @@ class FusedAdamW(torch.optim.Optimizer):
                       "exp_avg_sq": D.view(D.exp_avg_sq, i).clone()}
                 if p.dtype == torch.bfloat16:
                     st["master"] = D.view(D.master, i).clone()
+                if D.ema is not None:
+                    st["ema"] = D.view(D.ema, i).clone()
                 state[index[id(p)]] = st
         out = {"state": state, "param_groups": packed, "max_grad_norm": self.max_grad_norm,
                "skipped_steps": {str(D.device): int(D.block[_BLK_SKIPPED]) for D in self._devs.values()}}
+        if self.ema_decay is not None:
+            out["ema_decay"], out["ema_warmup"] = self.ema_decay, self.ema_warmup
         for hook in self._optimizer_state_dict_post_hooks.values():
             res = hook(self, out)
             out = out if res is None else res
@@ -279,7 +341,10 @@ class FusedAdamW(torch.optim.Optimizer):
         """accepts state_dict() of this class and of `torch.optim.AdamW` (no `master`: the masters are initialised from the parameters).
         Not the base class's: that one casts floating-point state to the PARAMETER's dtype, which would round the fp32 moments and masters
         of bf16 parameters to bf16.  Of a saved param group only lr / betas / eps / weight_decay are taken (torch's foreach, fused,
-        capturable ... mean nothing here; amsgrad / maximize are refused); `skipped_steps` is restored when present;
+        capturable ... mean nothing here; amsgrad / maximize are refused); `skipped_steps` is restored when present.  With `ema_decay`:
+        `ema` is restored where the dict has it and is otherwise the loaded master / parameter (a `torch.optim.AdamW` dict, a dict saved
+        without EMA, a parameter never stepped); `ema_decay` / `ema_warmup` are taken from a dict that has them.  Without: a dict's EMA
+        entries are ignored.
         `register_load_state_dict_pre_hook` / `_post_hook` hooks run."""
         for hook in self._optimizer_load_state_dict_pre_hooks.values():
             res = hook(self, state_dict)
@@ -294,6 +359,10 @@ class FusedAdamW(torch.optim.Optimizer):
             g.update({k: s[k] for k in _GROUP_KEYS if k in s})
         if "max_grad_norm" in state_dict:
             self.max_grad_norm = state_dict["max_grad_norm"]
+        if self.ema_decay is not None and state_dict.get("ema_decay") is not None:
+            if not 0.0 <= state_dict["ema_decay"] < 1.0:
+                raise ValueError(f"invalid ema_decay in the loaded state dict: {state_dict['ema_decay']}")
+            self.ema_decay, self.ema_warmup = float(state_dict["ema_decay"]), bool(state_dict.get("ema_warmup", self.ema_warmup))
         loaded = {id(ids[k]): v for k, v in state_dict["state"].items()}
         for D in self._devs.values():
             steps = [int(float(loaded[id(p)]["step"])) if id(p) in loaded else None for p, _ in D.params]
@@ -309,6 +378,9 @@ class FusedAdamW(torch.optim.Optimizer):
                     v.copy_(st["exp_avg_sq"])
                 if p.dtype == torch.bfloat16:
                     D.view(D.master, i).copy_(st["master"] if st is not None and "master" in st else p)
+                if D.ema is not None:
+                    weight = D.view(D.master, i) if p.dtype == torch.bfloat16 else p
+                    D.view(D.ema, i).copy_(st["ema"] if st is not None and "ema" in st else weight)
             D.step_base.copy_(torch.tensor([-1 if s is None else total - s for s in steps] or [-1], dtype=torch.int32))
             D.block[_BLK_STEP] = total
             D.block[_BLK_SKIPPED] = int(state_dict.get("skipped_steps", {}).get(str(D.device), 0))
