@@ -20,7 +20,7 @@ extern "C" {
 #endif
 
 enum { XCLIP_F32 = 0, XCLIP_BF16 = 1 };
-#define XCLIP_ABI_VERSION 29
+#define XCLIP_ABI_VERSION 30
 
 int xclip_abi_version(void);
 const char* xclip_last_error(void);
@@ -434,7 +434,12 @@ int xclip_neg_cosine_bwd(const void* p, const void* z, const float* cosv, const 
  *     the update above: ema += (1 - d_u) (w - ema) in fp32, w the fp32 master where there is one.  u = step of the state block (the applied
  *     steps including this one, >= 1), d_u = ema_warmup ? min(ema_decay, (1 + u) / (10 + u)) : ema_decay, 0 <= ema_decay < 1; 1 - d_u is
  *     formed in double and rounded once.  found_nonfinite: returns at once, ema keeps every bit; chunks that are not in the table are not
- *     averaged.  m, v, w and the parameter get exactly adamw_step's bits. */
+ *     averaged.  m, v, w and the parameter get exactly adamw_step's bits.
+ *   grad_accumulate (ABI 30): gradients of several backward passes summed in fp32 (FusedAdamW.accumulate_begin / accumulate /
+ *     accumulate_end; x_clip_amd/cached.py).  `acc`: one more flat fp32 array indexed by state_off as exp_avg, 16-byte aligned, zeroed by
+ *     the caller; chunks [chunk0, chunk0 + count), all of gradient dtype g_dtype (the parameter pointer of a record is not read).
+ *     materialise = 0: acc[state_off + i] += (float)g[i].  materialise = 1: g[i] = acc[state_off + i], rounded to nearest even once when
+ *     the gradient is bf16, a copy when it is fp32.  One thread per element: no atomics, bit-reproducible; inf / nan pass through. */
 int xclip_gradnorm_partial(const void* table, int64_t chunk0, int64_t count, int g_dtype, float* partials, void* stream);
 int xclip_optim_prepare(const float* partials, int64_t n_chunks, float max_norm, int clip, void* state_block, int32_t* step_base,
                         const int32_t* absent, int64_t n_absent, void* stream);
@@ -444,6 +449,7 @@ int xclip_adamw_step(const void* table, int64_t chunk0, int64_t count, int p_dty
 int xclip_adamw_ema_step(const void* table, int64_t chunk0, int64_t count, int p_dtype, int g_dtype, float* exp_avg, float* exp_avg_sq,
                          float* master, const void* state_block, int32_t* step_base, double lr, double beta1, double beta2, double eps,
                          double weight_decay, float* ema, double ema_decay, int ema_warmup, void* stream);
+int xclip_grad_accumulate(const void* table, int64_t chunk0, int64_t count, int g_dtype, float* acc, int materialise, void* stream);
 
 #ifdef __cplusplus
 }

@@ -4,6 +4,7 @@
 
 Python host code (this package) over a C-ABI HIP library (include/xclip.h, built by `python -m x_clip_amd.build`).
 """
+from .cached import CachedContrastiveStep  # noqa: F401
 from .clip import CLIP, TextTransformer, VisionTransformer  # noqa: F401
 from .metrics import contrastive_metrics  # noqa: F401
 from .optim import FusedAdamW  # noqa: F401
@@ -35,5 +36,5 @@ def set_batch_invariant(on: bool = True) -> bool:
 _small_limit_saved = None
 
 
-__all__ = ["CLIP", "TextTransformer", "VisionTransformer", "FusedAdamW", "contrastive_metrics", "similarity_topk", "zero_shot_classifier",
+__all__ = ["CLIP", "TextTransformer", "VisionTransformer", "FusedAdamW", "CachedContrastiveStep", "contrastive_metrics", "similarity_topk", "zero_shot_classifier",
            "set_batch_invariant"]

@@ -105,9 +105,10 @@ _SIGNATURES = {
     "xclip_optim_prepare": (c_int, [P, L, F, I, P, P, P, L, P]),
     "xclip_adamw_step": (c_int, [P, L, L, I, I, P, P, P, P, P, D, D, D, D, D, P]),
     "xclip_adamw_ema_step": (c_int, [P, L, L, I, I, P, P, P, P, P, D, D, D, D, D, P, D, I, P]),
+    "xclip_grad_accumulate": (c_int, [P, L, L, I, P, I, P]),
 }
 EXPORTS = tuple(_SIGNATURES)
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 
 def _bind(path: str):

@@ -516,7 +516,7 @@ class CLIP(nn.Module):
         self._no_single_latent("embed_text")
         text_args, text_kwargs = self._text_tower_call(text, text != self.text_pad_id, True)
         text_embeds = self._text_cls_embeds(self._encode_text(text_args, False, text_kwargs), text)
-        return XF.l2norm(XF.linear(text_embeds, self.to_text_latent.weight))
+        return self._text_latents(text_embeds, self.to_text_latent)
 
     @torch.no_grad()
     def embed_image(self, image):
@@ -524,7 +524,63 @@ class CLIP(nn.Module):
         forward(text, image, return_latents=True), same bits in eval() mode; x_clip.py:650-715, one side)."""
         self._no_single_latent("embed_image")
         image_embeds = self._image_cls_embeds(self._encode_image(image, False))
-        return XF.l2norm(XF.linear(image_embeds, self.to_visual_latent.weight))
+        return self._image_latents(image_embeds, self.to_visual_latent)
+
+    # ---- the pieces of forward that x_clip_amd.cached.CachedContrastiveStep runs slice by slice ----
+    @staticmethod
+    def _text_latents(text_embeds, proj):
+        return XF.l2norm(XF.linear(text_embeds, proj.weight))                               # x_clip.py:713
+
+    def _image_latents(self, image_embeds, proj):
+        if self.downsample_image_embeds:
+            return XF.l2norm(XF.downsample_latents(image_embeds, proj[1].weight, proj[2].weight, proj[2].bias))
+        return XF.l2norm(XF.linear(image_embeds, proj.weight))                              # x_clip.py:714-715
+
+    def _encode_towers(self, text_args, text_kwargs, image, freeze_image_encoder, freeze_text_encoder):
+        """-> (enc_text_parts, enc_image).  The two towers are independent until the head.  On a GPU the vision tower is issued on a side
+        HIP stream (autograd replays its backward there too), so its small kernels fill the gaps the text tower's leaves; the head waits
+        for both."""
+        side = self._side_stream(image.device) if self.overlap_towers else None
+        if side is not None:
+            main = torch.cuda.current_stream(image.device)
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                enc_image = self._encode_image(image, freeze_image_encoder)
+            enc_text_parts = self._encode_text(text_args, freeze_text_encoder, text_kwargs)
+            main.wait_stream(side)
+            enc_image.record_stream(main)
+        else:
+            enc_text_parts = self._encode_text(text_args, freeze_text_encoder, text_kwargs)
+            enc_image = self._encode_image(image, freeze_image_encoder)
+        return enc_text_parts, enc_image
+
+    def _cls_latents(self, text, image, freeze_image_encoder=False, freeze_text_encoder=False):
+        """text [b, seq], image [b, c, h, w] -> the l2-normalised CLS latents ([b, dim_latent] each) as forward computes them
+        (x_clip.py:650-715), in whatever mode (training / eval, grad / no grad) the caller is in"""
+        self._no_single_latent("_cls_latents")
+        text_args, text_kwargs = self._text_tower_call(text, text != self.text_pad_id, True)
+        enc_text_parts, enc_image = self._encode_towers(text_args, text_kwargs, image, freeze_image_encoder, freeze_text_encoder)
+        return (self._text_latents(self._text_cls_embeds(enc_text_parts, text), self.to_text_latent),
+                self._image_latents(self._image_cls_embeds(enc_image), self.to_visual_latent))
+
+    def _contrastive_spec(self, multiview_loss_weight=0):
+        cl_loss_weight = 1 - (self.text_ssl_loss_weight + self.image_ssl_loss_weight + multiview_loss_weight)     # x_clip.py:851-855
+        return XL.ContrastiveSpec(dcl=self.decoupled_contrastive_learning, main_weight=cl_loss_weight,
+                                  multiview_weight=multiview_loss_weight, distributed=self.requires_all_gather,
+                                  assume_equal_batch=self.assume_equal_batch, sigmoid=self.sigmoid_loss)
+
+    def _cls_head(self, text_latents, image_latents, text_latents_extra, image_latents_extra, spec):
+        """the CLS head on [views, b, dim_latent] latents: InfoNCE / DCL or the pairwise sigmoid loss, and -- track_metrics -- the
+        in-batch retrieval metrics of the first views"""
+        if self._metric_ks is not None:
+            from .metrics import contrastive_metrics
+            with torch.no_grad():
+                self.last_metrics = contrastive_metrics(text_latents[0].detach(), image_latents[0].detach(), self.temperature.detach(),
+                                                        ks=self._metric_ks, distributed=self.requires_all_gather,
+                                                        assume_equal_batch=self.assume_equal_batch)
+        if self.sigmoid_loss:
+            return XL.sigmoid_loss(self.temperature, self.logit_bias, text_latents, image_latents, spec)
+        return XL.contrastive_loss(self.temperature, text_latents, image_latents, text_latents_extra, image_latents_extra, spec)
 
     def _side_stream(self, device, which=0):
         if device.type != "cuda":
@@ -636,20 +692,7 @@ class CLIP(nn.Module):
         cls_row_only = not self.use_all_token_embeds and not return_encodings               # x_clip.py:708 reads `enc_text[:, 0]` alone
         text_args, text_kwargs = self._text_tower_call(text, text_mask, cls_row_only)
 
-        # The two towers are independent until the head.  On a GPU the vision tower is issued on a side HIP stream (autograd
-        # replays its backward there too), so its small kernels fill the gaps the text tower's leaves; the head waits for both.
-        side = self._side_stream(image.device) if self.overlap_towers else None
-        if side is not None:
-            main = torch.cuda.current_stream(image.device)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                enc_image = self._encode_image(image, freeze_image_encoder)
-            enc_text_parts = self._encode_text(text_args, freeze_text_encoder, text_kwargs)
-            main.wait_stream(side)
-            enc_image.record_stream(main)
-        else:
-            enc_text_parts = self._encode_text(text_args, freeze_text_encoder, text_kwargs)
-            enc_image = self._encode_image(image, freeze_image_encoder)
+        enc_text_parts, enc_image = self._encode_towers(text_args, text_kwargs, image, freeze_image_encoder, freeze_text_encoder)
         if return_encodings:                                                               # x_clip.py:697-698
             return self._join_text(enc_text_parts, text), enc_image
 
@@ -663,18 +706,13 @@ class CLIP(nn.Module):
             text_embeds = self._text_cls_embeds(enc_text_parts, text)
             image_embeds = self._image_cls_embeds(enc_image)
 
-        text_latents = XF.l2norm(XF.linear(text_embeds, self.to_text_latent.weight))       # x_clip.py:713-715
-        def visual_latents(proj):
-            if self.downsample_image_embeds:
-                return XF.downsample_latents(image_embeds, proj[1].weight, proj[2].weight, proj[2].bias)
-            return XF.linear(image_embeds, proj.weight)
-
-        image_latents = XF.l2norm(visual_latents(self.to_visual_latent))
+        text_latents = self._text_latents(text_embeds, self.to_text_latent)                 # x_clip.py:713-715
+        image_latents = self._image_latents(image_embeds, self.to_visual_latent)
 
         text_latents_extra, image_latents_extra = text_latents, image_latents              # x_clip.py:720-724
         if self.extra_latent_projection:
-            text_latents_extra = XF.l2norm(XF.linear(text_embeds, self.to_text_latent_extra.weight))
-            image_latents_extra = XF.l2norm(visual_latents(self.to_visual_latent_extra))
+            text_latents_extra = self._text_latents(text_embeds, self.to_text_latent_extra)
+            image_latents_extra = self._image_latents(image_embeds, self.to_visual_latent_extra)
 
         if return_latents:                                                                 # x_clip.py:728-732
             if self.extra_latent_projection:
@@ -700,28 +738,14 @@ class CLIP(nn.Module):
             image_latents_extra = split_views(image_latents_extra, num_batch_images)
 
         multiview_loss_weight = self.multiview_loss_weight if is_multiview else 0          # x_clip.py:851-855
-        cl_loss_weight = 1 - (self.text_ssl_loss_weight + self.image_ssl_loss_weight + multiview_loss_weight)
-
-        spec = XL.ContrastiveSpec(dcl=self.decoupled_contrastive_learning, main_weight=cl_loss_weight,
-                                  multiview_weight=multiview_loss_weight, distributed=self.requires_all_gather,
-                                  assume_equal_batch=self.assume_equal_batch, sigmoid=self.sigmoid_loss)
+        spec = self._contrastive_spec(multiview_loss_weight)
         if self.use_all_token_embeds:                                                      # x_clip.py:797-811
             loss = XL.filip_loss(self.temperature, text_latents, image_latents,
                                  text_latents_extra if self.extra_latent_projection else None,
                                  image_latents_extra if self.extra_latent_projection else None, text_mask, spec)
         else:
-            if self._metric_ks is not None:
-                from .metrics import contrastive_metrics
-                with torch.no_grad():
-                    self.last_metrics = contrastive_metrics(text_latents[0].detach(), image_latents[0].detach(), self.temperature.detach(),
-                                                            ks=self._metric_ks, distributed=self.requires_all_gather,
-                                                            assume_equal_batch=self.assume_equal_batch)
-            if self.sigmoid_loss:
-                loss = XL.sigmoid_loss(self.temperature, self.logit_bias, text_latents, image_latents, spec)
-            else:
-                loss = XL.contrastive_loss(self.temperature, text_latents, image_latents,
-                                           text_latents_extra if self.extra_latent_projection else None,
-                                           image_latents_extra if self.extra_latent_projection else None, spec)
+            loss = self._cls_head(text_latents, image_latents, text_latents_extra if self.extra_latent_projection else None,
+                                  image_latents_extra if self.extra_latent_projection else None, spec)
         if self.use_mlm:                                                                   # x_clip.py:857-860
             loss = loss + text_ssl_loss * self.text_ssl_loss_weight
         if self.use_visual_ssl:

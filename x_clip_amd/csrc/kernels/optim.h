@@ -11,6 +11,8 @@
 //   adamw_kernel              one work-group per chunk: returns at once when the gradients were not finite (the step is skipped ON THE
 //                             DEVICE); otherwise one streaming pass, fp32 arithmetic, in torch.optim.AdamW's operation order.
 //   adamw_ema_kernel          the same pass with a weight EMA kept beside the moments (FusedAdamW(ema_decay=...)): + 8 bytes per parameter.
+//   grad_accum_kernel         gradients of several backward passes summed into a flat fp32 array and rounded once into `.grad`
+//                             (FusedAdamW.accumulate_begin / accumulate / accumulate_end; x_clip_amd/cached.py).
 //
 // Algorithmic HBM traffic per parameter: bf16 2 (g, norm pass) + 2 (g) + 12 (m, v, master in) + 12 (out) + 2 (p out) = 30 bytes;
 // fp32 4 + 4 + 12 (m, v, p in) + 12 (out) = 32 bytes.  Everything is read once and written once: non-temporal hint, as in rows.h.
@@ -283,6 +285,41 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_ema_kernel(const OptChunk* 
         w[i] = wi;
         e[i] = ei;
         if (MASTER) p[i] = from_f32<P>(wi);
+    }
+}
+
+// ---- gradients of several backward passes, summed in fp32 ----------------------------------------------------------------------------------
+// FusedAdamW.accumulate*(): `acc` is one more flat fp32 array laid out as exp_avg.  One work-group per chunk of the same table, G the
+// gradient's storage type.  MATERIALISE = false: acc[state_off + i] += float(g[i]) (the gradient of one backward pass; a bf16 `.grad`
+// summed by autograd's own += would round to 8 bits after every pass).  MATERIALISE = true: g[i] = acc[state_off + i] rounded to
+// nearest even ONCE (fp32: a copy) -- what the norm pass and adamw_kernel then read.  Every element is owned by one thread: no atomics,
+// the same bits on every run; inf / nan pass through the sum and the rounding, so the step is still skipped on the device.
+// Traffic per bf16 gradient element: 2 (g) + 4 + 4 (acc in, out) = 10 bytes to add, 4 + 2 to materialise.
+template <typename G, bool MATERIALISE>
+__global__ __launch_bounds__(OPT_THREADS) void grad_accum_kernel(const OptChunk* __restrict__ table, int chunk0, float* __restrict__ acc) {
+    const OptChunk c = table[chunk0 + (int)blockIdx.x];
+    if (((c.dtypes >> 8) & 0xff) != OptDtype<G>::CODE) return;  // (a table that disagrees with the launch touches nothing)
+    const int tid = threadIdx.x;
+    G* g = reinterpret_cast<G*>(c.g);
+    float* a = acc + c.state_off;
+    const int nvec = (opt_aligned16(c.g) && (c.state_off & 3) == 0) ? c.n / 8 : 0;
+    for (int i = tid; i < nvec; i += OPT_THREADS) {
+        const long o = (long)i * 8;
+        float av[8];
+        opt_load8<true>(a + o, av);
+        if (MATERIALISE) {
+            opt_store8<false>(g + o, av);                      // (no hint: the norm pass reads the gradient next)
+        } else {
+            float gv[8];
+            opt_load8<true>(g + o, gv);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) av[j] += gv[j];
+            opt_store8<true>(a + o, av);
+        }
+    }
+    for (int i = nvec * 8 + tid; i < c.n; i += OPT_THREADS) {  // scalar tail / unaligned chunk
+        if (MATERIALISE) g[i] = from_f32<G>(a[i]);
+        else a[i] += to_f32(g[i]);
     }
 }
 

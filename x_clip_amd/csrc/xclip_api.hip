@@ -1862,4 +1862,17 @@ int xclip_adamw_ema_step(const void* table, int64_t chunk0, int64_t count, int p
     return check_launch(__func__);
 }
 
+int xclip_grad_accumulate(const void* table, int64_t chunk0, int64_t count, int g_dtype, float* acc, int materialise, void* stream) {
+    XC_REQUIRE(dtype_ok(g_dtype), "bad gradient dtype");
+    XC_REQUIRE(chunk0 >= 0 && count >= 0 && chunk0 + count < (1ll << 31), "bad chunk range");
+    if (count == 0) return 0;
+    XC_REQUIRE(table && acc && aligned16(table) && aligned16(acc), "null or misaligned pointer");
+    dim3 grid((unsigned)count), block(OPT_THREADS);
+    by_dtype(g_dtype, [&](auto t) { using T = typename decltype(t)::type;
+        if (materialise) hipLaunchKernelGGL((grad_accum_kernel<T, true>), grid, block, 0, (hipStream_t)stream, (const OptChunk*)table, (int)chunk0, acc);
+        else hipLaunchKernelGGL((grad_accum_kernel<T, false>), grid, block, 0, (hipStream_t)stream, (const OptChunk*)table, (int)chunk0, acc);
+    });
+    return check_launch(__func__);
+}
+
 }  // extern "C"

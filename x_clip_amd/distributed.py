@@ -237,7 +237,10 @@ class GradSync:
     hop; over 8 ranks the cancelling column-sum gradients (biases, gains) lose a digit (tests/test_distributed_gpu.py measures both).
     Costs twice the bytes on the wire and two casting passes; the weight-gradient GEMMs then no longer write in place.
 
-    Unsupported: gradient accumulation over several backward passes without a `finish()` between them (a bucket is reduced once per step)."""
+    Gradient accumulation over several backward passes without a `finish()` between them (a bucket is reduced once per step) goes through
+    `FusedAdamW.accumulate_begin / accumulate / accumulate_end` with `overlap=False` -- the sum is kept in fp32 outside `.grad`, each pass
+    writes into the slices again (`release`), `accumulate_end()` writes the rounded sum into them and `finish()` reduces that:
+    `x_clip_amd.cached.CachedContrastiveStep`.  Autograd's own `+=` over several backward passes under `overlap=True` stays unsupported."""
 
     def __init__(self, module: torch.nn.Module, group=None, overlap: bool = True, reduce_dtype: Optional[torch.dtype] = None,
                  bucket_bytes: int = 12 << 20):
@@ -390,6 +393,11 @@ class GradSync:
             return None
         self._claimed.add(id(p))
         return self._view(p)
+
+    def release(self, p: Tensor) -> None:
+        """grad sink protocol: the gradient this step's backward wrote for parameter `p` has been consumed and `.grad` dropped
+        (FusedAdamW.accumulate): its slice may be claimed again in this step"""
+        self._claimed.discard(id(p))
 
     # ---- hooks ----
     def _make_hook(self, bi):

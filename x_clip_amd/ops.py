@@ -1413,3 +1413,13 @@ def adamw_ema_step(table: Tensor, chunk0: int, count: int, param_dtype, grad_dty
                                                exp_avg_sq.data_ptr(), _ptr(master), block.data_ptr(), step_base.data_ptr(), float(lr),
                                                float(beta1), float(beta2), float(eps), float(weight_decay), ema.data_ptr(), float(ema_decay),
                                                int(bool(ema_warmup)), _stream(table)), "xclip_adamw_ema_step")
+
+
+def grad_accumulate(table: Tensor, chunk0: int, count: int, grad_dtype, acc: Tensor, materialise: bool = False) -> None:
+    """chunks [chunk0, chunk0 + count) of one gradient dtype: acc[state_off + i] += float(g[i]) in fp32, or -- `materialise` --
+    g[i] = acc[state_off + i] rounded to nearest even once (a copy for fp32 gradients).  `acc`: flat fp32, laid out as exp_avg"""
+    _dev_check(table, acc)
+    assert table.dtype == torch.uint8 and table.numel() >= (chunk0 + count) * OPTIM_CHUNK_BYTES
+    assert acc.dtype == torch.float32
+    _lib.check(_lib.lib().xclip_grad_accumulate(table.data_ptr(), chunk0, count, _DTYPES[grad_dtype], acc.data_ptr(), int(bool(materialise)),
+                                                _stream(table)), "xclip_grad_accumulate")

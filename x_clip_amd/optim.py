@@ -67,6 +67,8 @@ class _DeviceState:
         self.n_chunks = self.n_absent = 0
         self.segments = []                                      # (first chunk, chunks, param group, parameter dtype, gradient dtype)
         self.norm_segments = []                                 # (first chunk, chunks, gradient dtype)
+        self.acc = None                                         # accumulate_begin(): flat fp32 sum of gradients, laid out as exp_avg
+        self.acc_grad = {}                                      # parameter index -> the `.grad` tensor accumulate_end() wrote last time
 
     def view(self, flat, i):
         p = self.params[i][0]
@@ -99,6 +101,9 @@ class FusedAdamW(torch.optim.Optimizer):
       the EMA bit-identical) and the applied step count u behind `ema_warmup` (d = min(ema_decay, (1 + u) / (10 + u)), timm's ramp).
       Initialised to the weights (exact); parameters without a gradient are not averaged.  `state[p]["ema"]` is a view of the flat array;
       `with opt.ema_weights():` evaluates or checkpoints the model on the averaged weights.
+    * `accumulate_begin()` / `accumulate()` / `accumulate_end()` sum the gradients of several backward passes in a flat fp32 array
+      (4 bytes per parameter, allocated at the first `accumulate_begin()`) and round the sum once into `.grad`; `step()` itself is
+      unchanged and raises while a sum is open.  `x_clip_amd.cached.CachedContrastiveStep` is built on them.
 
     Streams: `step()` runs on the current stream.  The backward's side streams join the current stream before `backward()` returns; with
     `GradSync` call `sync.finish()` FIRST (it orders the current stream behind the all-reduces).  Distributed training needs nothing else:
@@ -126,6 +131,8 @@ class FusedAdamW(torch.optim.Optimizer):
         self.ema_decay = None if ema_decay is None else float(ema_decay)
         self.ema_warmup = bool(ema_warmup)
         self._ema_swapped = False                               # inside `with ema_weights():`
+        self._accumulating = False                              # between accumulate_begin() and accumulate_end()
+        self._accumulated = {}                                  # id(param) -> param: what accumulate() has taken a gradient from
         self._devs = None
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.max_grad_norm = max_grad_norm
@@ -230,23 +237,30 @@ class FusedAdamW(torch.optim.Optimizer):
             D.staged[slot] = torch.cuda.current_stream(D.device).record_event()
         self.table_uploads += 1
 
+    def _sync_table(self, D: _DeviceState):
+        """the chunk table describes the gradients the parameters hold right now (rebuilt and uploaded only when it does not)"""
+        grads = [p.grad for p, _ in D.params]
+        # (address, dtype AND layout: a strided or reshaped gradient swapped in at the same address must reach _rebuild's checks)
+        signature = tuple((p.data_ptr(), None if g is None else (g.data_ptr(), g.dtype, g.shape == p.shape and g.is_contiguous()))
+                          for (p, _), g in zip(D.params, grads))
+        if signature != D.signature:
+            self._rebuild(D, grads)
+            D.signature = signature
+
     @torch.no_grad()
     def step(self, closure=None):
         if self._ema_swapped:
             raise RuntimeError("x_clip_amd FusedAdamW: step() inside `with ema_weights():` -- the parameters hold the averaged weights")
+        if self._accumulating:
+            raise RuntimeError("x_clip_amd FusedAdamW: step() between accumulate_begin() and accumulate_end() -- `.grad` holds one backward "
+                               "pass, not the sum")
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
         dt = {0: torch.float32, 1: torch.bfloat16}
         for D in self._devs.values():
-            grads = [p.grad for p, _ in D.params]
-            # (address, dtype AND layout: a strided or reshaped gradient swapped in at the same address must reach _rebuild's checks)
-            signature = tuple((p.data_ptr(), None if g is None else (g.data_ptr(), g.dtype, g.shape == p.shape and g.is_contiguous()))
-                              for (p, _), g in zip(D.params, grads))
-            if signature != D.signature:
-                self._rebuild(D, grads)
-                D.signature = signature
+            self._sync_table(D)
             if D.n_chunks == 0:
                 continue
             ctx = torch.cuda.device(D.device) if D.device.type == "cuda" else _null()
@@ -264,6 +278,87 @@ class FusedAdamW(torch.optim.Optimizer):
                                            g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], D.ema, self.ema_decay,
                                            self.ema_warmup)
         return loss
+
+    # ---- gradients of several backward passes ----
+    @torch.no_grad()
+    def accumulate_begin(self):
+        """Open a sum of gradients over several backward passes (x_clip_amd.cached.CachedContrastiveStep; plain gradient accumulation):
+
+            opt.accumulate_begin()
+            for micro in batch: loss(micro).backward(); opt.accumulate()
+            opt.accumulate_end();  sync.finish();  opt.step();  opt.zero_grad()
+
+        The sum lives in a flat fp32 array laid out as `exp_avg` (4 bytes per parameter, allocated at the first call, zeroed at every
+        call): autograd's own `+=` into the `.grad` of a bf16 model rounds to an 8-bit mantissa after every pass.  Not part of
+        `state_dict()`: it is empty between steps.  An optimizer that never calls this allocates and launches nothing for it."""
+        if self._accumulating:
+            raise RuntimeError("x_clip_amd FusedAdamW: accumulate_begin() twice without accumulate_end()")
+        for D in self._devs.values():
+            if D.acc is None:
+                D.acc = torch.zeros_like(D.exp_avg)
+            else:
+                D.acc.zero_()
+        self._accumulated = {}
+        self._accumulating = True
+
+    def _accumulate_launch(self, D: _DeviceState, materialise: bool):
+        self._sync_table(D)
+        if D.n_chunks == 0:
+            return
+        dt = {0: torch.float32, 1: torch.bfloat16}
+        with (torch.cuda.device(D.device) if D.device.type == "cuda" else _null()):
+            for c0, n, gc in D.norm_segments:
+                ops.grad_accumulate(D.table, c0, n, dt[gc], D.acc, materialise)
+
+    @torch.no_grad()
+    def accumulate(self):
+        """After a backward pass: every parameter's `.grad` (fp32 or bf16, wherever autograd or `GradSync.claim` put it) is added into
+        its slice of the fp32 sum -- one launch per gradient dtype over the same chunk table `step()` walks -- and `.grad` is set to
+        None, so that the next backward writes a fresh gradient (a `GradSync` slice is handed back to the sink and claimed again).
+        Runs on the current stream; nothing is read back.  Parameters without a gradient in this pass are left alone."""
+        if not self._accumulating:
+            raise RuntimeError("x_clip_amd FusedAdamW: accumulate() outside accumulate_begin() ... accumulate_end()")
+        from . import functional as XF
+        sinks = [s for s in XF.grad_sinks() if hasattr(s, "release")]
+        for D in self._devs.values():
+            self._accumulate_launch(D, False)
+            for p, _ in D.params:
+                if p.grad is not None:
+                    self._accumulated[id(p)] = p
+                    p.grad = None
+                    for sink in sinks:
+                        sink.release(p)
+
+    @torch.no_grad()
+    def accumulate_end(self):
+        """Close the sum: every parameter accumulate() took a gradient from gets a `.grad` of its own dtype holding the fp32 sum rounded
+        to nearest even ONCE -- in its `GradSync` slice where the sink hands one out, otherwise in a tensor this optimizer keeps (from
+        the second step on the addresses, and with them the chunk table, are stable).  Afterwards `sync.finish()`, clipping, the skip
+        decision (a non-finite gradient in any pass is a non-finite sum) and `step()` run unchanged on `.grad`."""
+        if not self._accumulating:
+            raise RuntimeError("x_clip_amd FusedAdamW: accumulate_end() without accumulate_begin()")
+        from . import functional as XF
+        for D in self._devs.values():
+            pending = [i for i, (p, _) in enumerate(D.params) if p.grad is not None]
+            if pending:
+                raise RuntimeError(f"x_clip_amd FusedAdamW: accumulate_end(): {len(pending)} parameter(s) hold a gradient that accumulate() has "
+                                   "not taken -- call accumulate() after the last backward pass")
+            for i, (p, _) in enumerate(D.params):
+                if id(p) not in self._accumulated:
+                    continue
+                out = None
+                for sink in XF.grad_sinks():
+                    out = sink.claim(p, p.shape, p.dtype)
+                    if out is not None:
+                        break
+                if out is None:
+                    out = D.acc_grad.get(i)
+                    if out is None or out.dtype != p.dtype or out.device != p.device:
+                        out = D.acc_grad[i] = torch.empty_like(p, memory_format=torch.contiguous_format)
+                p.grad = out
+            self._accumulate_launch(D, True)
+        self._accumulated = {}
+        self._accumulating = False
 
     # ---- the averaged weights ----
     @contextmanager
