@@ -20,7 +20,7 @@ extern "C" {
 #endif
 
 enum { XCLIP_F32 = 0, XCLIP_BF16 = 1 };
-#define XCLIP_ABI_VERSION 30
+#define XCLIP_ABI_VERSION 31
 
 int xclip_abi_version(void);
 const char* xclip_last_error(void);
@@ -75,6 +75,16 @@ int xclip_text_embed_fwd(const int64_t* tokens, const void* E, const void* P, co
 /* fp32 accumulators: dE [vocab, dim], dP [n, dim] (may be NULL), dcls [dim] (NULL when has_cls = 0) */
 int xclip_text_embed_bwd(const void* dout, const int64_t* tokens, float* dE_accum, float* dP_accum, float* dcls_accum,
                          int64_t batch, int64_t n, int64_t dim, int64_t vocab, int has_cls, int dtype, void* stream);
+/* The same embedding for a PACKED batch (x_clip.py:320-331 restricted to the rows the key-padding mask of x_clip.py:614,334 keeps): `rows`
+ * kept rows laid end to end, sample s in rows cu[s] .. cu[s+1].  tok [rows] int64 = the row's token id (ignored on CLS rows), pos [rows] int32 =
+ * its position inside its sample, position 0 being the CLS row when cls != NULL:  out[r] = cls if cls && pos[r] == 0, else
+ * E[tok[r]] + P[pos[r] - (cls != NULL)] (P may be NULL; it has `npos` rows).  Ids outside [0, vocab) and positions outside the table give a
+ * NaN row and set *bad_token_flag, as above.  Bit-equal to the kept rows of xclip_text_embed_fwd.
+ * Backward: dcls_accum [dim] fp32 += the column sum of dout over the CLS rows cu[0 .. batch) (a model with a CLS row).  dE and dP are segmented
+ * sums: xclip_sort_ids on the packed ids / positions, then xclip_scatter_add_sorted (n_in = n_out = 1) -- no [batch, n + 1, dim] array. */
+int xclip_text_embed_packed_fwd(const int64_t* tok, const int32_t* pos, const void* E, const void* P, const void* cls, void* out,
+                                int64_t rows, int64_t dim, int64_t vocab, int64_t npos, int32_t* bad_token_flag, int dtype, void* stream);
+int xclip_text_embed_packed_bwd(const void* dout, const int32_t* cu, float* dcls_accum, int64_t batch, int64_t dim, int dtype, void* stream);
 
 /* ---- patchify 'b c (h p1) (w p2) -> b (h w) (p1 p2 c)' (x_clip.py:357) with the PatchDropout keep-set
  * (x_clip.py:140-151) folded in: out[(b,i), :] = patch keep[b*nkeep + i] of image b (keep NULL: identity, nkeep =
@@ -217,6 +227,21 @@ int xclip_attention_pool_fwd(const void* q, const void* kv, const uint8_t* mask,
 int xclip_attention_pool_bwd(const void* q, const void* kv, const uint8_t* mask, const void* out, const void* dout, const float* lse,
                              void* dq, void* dkv, int64_t batch, int64_t n, int64_t heads, int64_t head_dim, float scale,
                              int64_t visible_keys, int dtype, void* stream);
+/* The same attention over samples of DIFFERENT lengths laid end to end (the packed text tower): Attention.forward x_clip.py:213-245 under the
+ * key-padding mask of x_clip.py:334, computed on the kept rows only -- a masked key has probability exactly 0 in the dense form, and a masked
+ * query row is read by nobody under the CLS head (x_clip.py:708).
+ * qkv [rows, 3, heads, head_dim]; cu [batch + 1] int32 ascending, cu[0] = 0, cu[batch] = rows: sample s owns rows cu[s] .. cu[s+1], 1 <= its
+ * length <= max_len (a unit longer than max_len is left unwritten).  Every key of a sample is visible to every query of that sample and to no
+ * other: no mask, no causal flag, no dropout.  scale > 0.
+ * out [rows, heads * head_dim]; lse [heads, rows] fp32, HEAD-major: the natural log-sum-exp of a row's scaled scores (the convention above);
+ * dqkv [rows, 3, heads, head_dim] fully overwritten.  Nothing outside rows [0, rows) is written; no atomics, a fixed summation order.
+ * bf16 with head_dim 64 and max_len <= 288 runs the head-resident MFMA kernels (K / V of a (sample, head) unit in LDS); anything else a plain
+ * one-wave-per-(row, head) form. */
+int xclip_attention_varlen_fwd(const void* qkv, const int32_t* cu, void* out, float* lse, int64_t rows, int64_t batch, int64_t heads,
+                               int64_t head_dim, int64_t max_len, float scale, int dtype, void* stream);
+int xclip_attention_varlen_bwd(const void* qkv, const int32_t* cu, const void* out, const void* dout, const float* lse, void* dqkv,
+                               int64_t rows, int64_t batch, int64_t heads, int64_t head_dim, int64_t max_len, float scale, int dtype,
+                               void* stream);
 /* Feed-forward dropout (nn.Dropout between the inner LayerNorm and the second Linear, x_clip.py:193-194): y[i] = x[i] keep(i) / (1 - p)
  * over n contiguous elements (n a multiple of the 16-byte chunk), keep(i) iff drop_hash(seed, i) >= p 2^32.  The same call on the
  * gradient is the backward; y == x is allowed. */

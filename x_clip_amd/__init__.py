@@ -8,6 +8,7 @@ from .cached import CachedContrastiveStep  # noqa: F401
 from .clip import CLIP, TextTransformer, VisionTransformer  # noqa: F401
 from .metrics import contrastive_metrics  # noqa: F401
 from .optim import FusedAdamW  # noqa: F401
+from .packing import TextLayout, text_layout  # noqa: F401
 from .retrieval import similarity_topk, zero_shot_classifier  # noqa: F401
 
 
@@ -37,4 +38,4 @@ _small_limit_saved = None
 
 
 __all__ = ["CLIP", "TextTransformer", "VisionTransformer", "FusedAdamW", "CachedContrastiveStep", "contrastive_metrics", "similarity_topk", "zero_shot_classifier",
-           "set_batch_invariant"]
+           "set_batch_invariant", "text_layout", "TextLayout"]

@@ -34,6 +34,8 @@ _SIGNATURES = {
     "xclip_l2norm_bwd": (c_int, [P, P, P, P, L, L, I, P]),
     "xclip_text_embed_fwd": (c_int, [P, P, P, P, P, L, L, L, L, P, I, P]),
     "xclip_text_embed_bwd": (c_int, [P, P, P, P, P, L, L, L, L, I, I, P]),
+    "xclip_text_embed_packed_fwd": (c_int, [P, P, P, P, P, P, L, L, L, L, P, I, P]),
+    "xclip_text_embed_packed_bwd": (c_int, [P, P, P, L, L, I, P]),
     "xclip_patchify": (c_int, [P, P, P, L, L, L, L, L, L, L, I, P]),
     "xclip_token_mean_fwd": (c_int, [P, L, P, L, L, L, I, P]),
     "xclip_token_mean_bwd": (c_int, [P, P, L, P, L, L, L, I, P]),
@@ -60,6 +62,8 @@ _SIGNATURES = {
     "xclip_attention_bwd": (c_int, [P, P, P, P, P, P, P, L, L, L, L, F, I, F, U, I, P]),
     "xclip_attention_pool_fwd": (c_int, [P, P, P, P, P, L, L, L, L, F, L, I, P]),
     "xclip_attention_pool_bwd": (c_int, [P, P, P, P, P, P, P, P, L, L, L, L, F, L, I, P]),
+    "xclip_attention_varlen_fwd": (c_int, [P, P, P, P, L, L, L, L, L, F, I, P]),
+    "xclip_attention_varlen_bwd": (c_int, [P, P, P, P, P, P, L, L, L, L, L, F, I, P]),
     "xclip_dropout": (c_int, [P, P, L, F, U, I, P]),
     "xclip_filip_reduce": (c_int, [P, L, P, P, P, P, L, P, P, P, L, L, L, L, L, L, I, P]),
     "xclip_filip_fused_ok": (c_int, [L, L, L, I]),
@@ -108,7 +112,7 @@ _SIGNATURES = {
     "xclip_grad_accumulate": (c_int, [P, L, L, I, P, I, P]),
 }
 EXPORTS = tuple(_SIGNATURES)
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 
 def _bind(path: str):

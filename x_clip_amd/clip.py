@@ -208,11 +208,17 @@ class TextTransformer(nn.Module):
         self.cls_token = nn.Parameter(torch.randn(dim)) if not causal else None            # x_clip.py:314
         self.transformer = Transformer(dim, dim_head=dim_head, causal=causal, **kwargs)
 
-    def forward(self, x, mask=None, *, pool_row: Optional[int] = None):
+    def forward(self, x, mask=None, *, pool_row: Optional[int] = None, layout=None):
         """pool_row = r (not a reference keyword): the caller will read row r of every sample's encoding and nothing else -- the result is
-        then [b, dim], and the last layer's row-wise part (to_out, feed-forward, norm_out) runs on those rows alone (functional.stack_forward)"""
+        then [b, dim], and the last layer's row-wise part (to_out, feed-forward, norm_out) runs on those rows alone (functional.stack_forward).
+        layout (packing.TextLayout of x under its key mask; CLIP.pack_text): the tower runs on the kept rows only and returns the CLS rows [b, dim]"""
         t = self.transformer
         pos = self.abs_pos_emb.weight if exists(self.abs_pos_emb) else None
+        if layout is not None:
+            if layout.batch != x.shape[0] or layout.n != x.shape[1]:
+                raise ValueError(f"text_layout was built for a [{layout.batch}, {layout.n}] token batch, the text is {tuple(x.shape)}")
+            return XF.text_encode_packed(layout, self.token_emb.weight, pos, self.cls_token, t.stack_params(),
+                                         t.spec(rotary=self.rotary_pos_emb.frequencies(x.device) if exists(self.rotary_pos_emb) else None))
         return XF.text_encode(x, mask, self.token_emb.weight, pos, self.cls_token, t.stack_params(),
                               t.spec(rotary=self.rotary_pos_emb.frequencies(x.device) if exists(self.rotary_pos_emb) else None), pool_row=pool_row)
 
@@ -438,6 +444,9 @@ class CLIP(nn.Module):
         # the CLS head reads one row of the text encoding (x_clip.py:708): ask the tower for that row only (forward(): `pool_row`).  Off = the
         # dense last layer, as the reference computes it (same loss and gradients either way)
         self.prune_unused_rows = True
+        # opt-in: the text tower runs on the rows its key mask keeps and nothing else (x_clip_amd.packing; README "Packed text tower").  Same
+        # tokens, same loss and gradients; padded rows are never computed.  Off: every launch as before.  Raises for what reads every row
+        self._pack_text = False
         # >1: the text batch runs through the text tower in that many slices, each on its own HIP stream.  The tower alternates
         # MFMA-bound GEMMs with HBM-bound row kernels; with two slices in flight one slice's LayerNorm / GEGLU kernels (no LDS, few
         # registers: they fit on a CU beside a persistent GEMM work-group) run under the other slice's GEMMs.  Encoders are row
@@ -477,14 +486,58 @@ class CLIP(nn.Module):
         if self.use_all_token_embeds:
             raise NotImplementedError(f"CLIP.{what}: use_all_token_embeds (the fine-grained head) has no single latent per sample")
 
+    # ---- the packed text tower (x_clip_amd.packing) ----
+    @property
+    def pack_text(self) -> bool:
+        return self._pack_text
+
+    @pack_text.setter
+    def pack_text(self, on):
+        if on:
+            self._check_pack_text()
+        self._pack_text = bool(on)
+
+    def _check_pack_text(self):
+        """pack_text drops the rows the key mask hides, so whatever reads every row, or indexes by dense position, is out (the message names the option)"""
+        tt = self.text_transformer
+        why = None
+        if not isinstance(tt, TextTransformer):
+            why = "a pluggable text_encoder (only the built-in TextTransformer has a packed form)"
+        elif self.use_all_token_embeds:
+            why = "use_all_token_embeds (the fine-grained head reads every token row)"
+        elif self.use_mlm:
+            why = "use_mlm (the masked-language-model head reads every token row)"
+        elif self.text_causal_mask:
+            why = "text_causal_mask (EOS pooling reads a row that depends on the tokens, under a causal mask)"
+        elif exists(tt.rotary_pos_emb):
+            why = "text_rotary_pos_emb (the rotary kernel takes a row's position from its dense index)"
+        elif not self.text_has_cls_token or not exists(tt.cls_token):
+            why = "text_has_cls_token=False (the packed tower returns the CLS row)"
+        elif self.text_encode_without_mask:
+            why = "text_encode_without_mask (without a key mask the padded rows are attended to: nothing can be dropped)"
+        elif tt.transformer.training and (tt.transformer.attn_dropout > 0. or tt.transformer.ff_dropout > 0.):
+            why = "attn_dropout / ff_dropout in the text tower (the keep-masks are indexed by dense position)"
+        if why is not None:
+            raise NotImplementedError(f"CLIP.pack_text is not available with {why}")
+
     # ---- what forward and the one-tower entry points share (x_clip.py:650-715) ----
-    def _text_tower_call(self, text, text_mask, cls_row_only):
+    def _text_tower_call(self, text, text_mask, cls_row_only, layout=None):
         """-> (args, kwargs) of the text tower.  `cls_row_only`: the caller reads `enc_text[:, 0]` and nothing else (x_clip.py:708) -- the
         tower is then asked for that row only and runs the row-wise part of its last layer on it (functional.stack_forward `pool_row`;
         the same loss and gradients up to bf16 rounding order: the other rows of that part are dead in the forward and their gradient is
-        exactly zero in the backward).  `prune_unused_rows = False` keeps the dense last layer."""
+        exactly zero in the backward).  `prune_unused_rows = False` keeps the dense last layer.
+        `pack_text`: the tower gets the packed layout of the batch (`layout`, or built here from the device tokens: one read of its row
+        count, packing.text_layout) and returns the CLS rows."""
         text_args = (text,) if self.text_encode_without_mask else (text, text_mask)
         text_kwargs = None
+        if self._pack_text:
+            self._check_pack_text()                              # (dropout and train / eval mode are only known now)
+            if not cls_row_only:
+                raise NotImplementedError("CLIP.pack_text is not available with return_encodings=True (the encoding of every row is returned)")
+            from .packing import text_layout
+            return text_args, dict(layout=layout if layout is not None else text_layout(text, self.text_pad_id, mask=text_mask))
+        if layout is not None:
+            raise ValueError("text_layout was passed but CLIP.pack_text is off")
         if (cls_row_only and self.prune_unused_rows and isinstance(self.text_transformer, TextTransformer) and self.text_has_cls_token
                 and not self.text_causal_mask):
             text_kwargs = dict(pool_row=0)
@@ -594,7 +647,7 @@ class CLIP(nn.Module):
     def _encode_text(self, text_args, freeze, kwargs=None):
         """-> list of encodings, one per slice of the batch (a single entry unless text_micro_batches > 1 applies)"""
         k, dev, b = int(self.text_micro_batches), text_args[0].device, text_args[0].shape[0]
-        if k <= 1 or b % k != 0 or b // k < self._micro_batch_min_rows:
+        if k <= 1 or b % k != 0 or b // k < self._micro_batch_min_rows or (kwargs is not None and "layout" in kwargs):   # (a packed batch is one slice)
             return [model_forward_with_context(fn=self.text_transformer, args=text_args, freeze=freeze, kwargs=kwargs)]
         bs = b // k
         on_gpu = dev.type == "cuda"                              # (CPU = the test build: the slices simply run one after the other)
@@ -653,8 +706,11 @@ class CLIP(nn.Module):
         freeze_text_encoder=False,
         text_to_image=True,
         aug_text=None,
-        aug_image=None
+        aug_image=None,
+        text_layout=None
     ):
+        """text_layout (not a reference keyword; needs `pack_text`): packing.text_layout(text, pad_id=text_pad_id) built ahead of time, e.g. from
+        the loader's CPU tokens -- the step then reads nothing back from the device.  Augmented texts get their own layout here, through the same code."""
         batch, device = text.shape[0], text.device
 
         text_mask = text != self.text_pad_id                                               # x_clip.py:614
@@ -674,6 +730,9 @@ class CLIP(nn.Module):
             num_batch_texts = len(aug_text) + 1
             aug_text = torch.cat(aug_text, dim=0)
             aug_text_mask = aug_text != self.text_pad_id
+            if exists(text_layout):
+                from .packing import cat_layouts, text_layout as make_layout
+                text_layout = cat_layouts([text_layout, make_layout(aug_text, self.text_pad_id)])
             text_mask = torch.cat((text_mask, aug_text_mask), dim=0)
             text = torch.cat((text, aug_text), dim=0)
 
@@ -690,7 +749,7 @@ class CLIP(nn.Module):
         assert not (self.multiview_loss_weight == 0 and is_multiview), 'multiview loss weight cannot be 0 if augmented text or images passed in'
 
         cls_row_only = not self.use_all_token_embeds and not return_encodings               # x_clip.py:708 reads `enc_text[:, 0]` alone
-        text_args, text_kwargs = self._text_tower_call(text, text_mask, cls_row_only)
+        text_args, text_kwargs = self._text_tower_call(text, text_mask, cls_row_only, text_layout)
 
         enc_text_parts, enc_image = self._encode_towers(text_args, text_kwargs, image, freeze_image_encoder, freeze_text_encoder)
         if return_encodings:                                                               # x_clip.py:697-698

@@ -26,6 +26,7 @@
 #include "kernels/sigloss.h"
 #include "kernels/sort.h"
 #include "kernels/tokens.h"
+#include "kernels/embed_packed.h"
 
 using namespace xc;
 using namespace xcapi;
@@ -657,6 +658,39 @@ int xclip_text_embed_bwd(const void* dout, const int64_t* tokens, float* dE_accu
     dim3 grid((unsigned)(n + (has_cls ? 1 : 0)), ysplit), block(256);
     const size_t red_bytes = (size_t)3 * dim * sizeof(float);
 #define F(T, C) hipLaunchKernelGGL((text_embed_bwd_kernel<T, C>), grid, block, red_bytes, (hipStream_t)stream, (const T*)dout, (const long long*)tokens, dE_accum, dP_accum, dcls_accum, (int)batch, (int)n, (int)dim, has_cls ? 1 : 0, (long long)vocab)
+    XC_DISPATCH_ROW(dtype, cpl, F);
+#undef F
+    return check_launch(__func__);
+}
+
+int xclip_text_embed_packed_fwd(const int64_t* tok, const int32_t* pos, const void* E, const void* P, const void* cls, void* out,
+                                int64_t rows, int64_t dim, int64_t vocab, int64_t npos, int32_t* bad_token_flag, int dtype, void* stream) {
+    XC_REQUIRE(dtype_ok(dtype), "bad dtype");
+    XC_REQUIRE(vocab > 0 && rows >= 0 && npos >= 0, "vocab must be positive, rows and npos non-negative");
+    XC_REQUIRE(dim > 0 && dim % vec_of(dtype) == 0, "dim must be a multiple of the 16-byte chunk");
+    XC_REQUIRE(aligned16(E) && aligned16(P) && aligned16(cls) && aligned16(out), "pointers must be 16-byte aligned");
+    if (rows == 0) return 0;
+    XC_REQUIRE(tok && pos && E && out, "null pointer");
+    dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((text_embed_packed_fwd_kernel<T>), grid, block, 0, (hipStream_t)stream, (const long long*)tok, (const int*)pos,
+                           (const T*)E, (const T*)P, (const T*)cls, (T*)out, (long)rows, (int)dim, (long long)vocab, (int)npos, bad_token_flag);
+    });
+    return check_launch(__func__);
+}
+
+int xclip_text_embed_packed_bwd(const void* dout, const int32_t* cu, float* dcls_accum, int64_t batch, int64_t dim, int dtype, void* stream) {
+    XC_REQUIRE(dtype_ok(dtype), "bad dtype");
+    const int vec = vec_of(dtype);
+    XC_REQUIRE(dim > 0 && dim % vec == 0, "dim must be a multiple of the 16-byte chunk");
+    XC_REQUIRE(dout && cu && dcls_accum && aligned16(dout), "pointers must be non-null, dout 16-byte aligned");
+    if (batch <= 0) return 0;
+    const int cpl = chunks_per_lane(dim, vec);
+    int split = (int)((batch + 31) / 32);
+    if (split > 16) split = 16;
+    dim3 grid((unsigned)split), block(256);
+    const size_t red_bytes = (size_t)3 * dim * sizeof(float);
+#define F(T, C) hipLaunchKernelGGL((text_embed_packed_dcls_kernel<T, C>), grid, block, red_bytes, (hipStream_t)stream, (const T*)dout, (const int*)cu, dcls_accum, (int)batch, (int)dim)
     XC_DISPATCH_ROW(dtype, cpl, F);
 #undef F
     return check_launch(__func__);

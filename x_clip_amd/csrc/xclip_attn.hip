@@ -13,6 +13,7 @@
 #include "kernels/attention6.h"
 #include "kernels/attention7.h"
 #include "kernels/attention_pool.h"
+#include "kernels/attention_varlen.h"
 
 using namespace xc;
 using namespace xcapi;
@@ -296,6 +297,80 @@ int xclip_attention_pool_bwd(const void* q, const void* kv, const uint8_t* mask,
     p.q = q; p.kv = kv; p.mask = mask; p.out = const_cast<void*>(out); p.lse = const_cast<float*>(lse); p.dout = dout; p.dq = dq; p.dkv = dkv;
     p.batch = (int)batch; p.n = (int)n; p.heads = (int)heads; p.nvis = (int)visible_keys; p.scale = scale;
     by_dtype(dtype, [&](auto t) { launch_attn_pool<typename decltype(t)::type>(p, head_dim, true, (hipStream_t)stream); });
+    return check_launch(__func__);
+}
+
+}  // extern "C"
+
+// ---- samples of different lengths laid end to end (kernels/attention_varlen.h) ----
+// the common checks and fields of both entry points; -> 0, or 1 with the error recorded under `fn`
+static int attn_varlen_setup(const char* fn, const void* qkv, const int32_t* cu, int64_t rows, int64_t batch, int64_t heads, int64_t head_dim,
+                             int64_t max_len, float scale, int dtype, bool ptrs_ok, xc::AttnVarlenParams& p) {
+#define XC_REQ(cond, msg) do { if (!(cond)) return xcapi::fail(fn, msg); } while (0)
+    XC_REQ(xcapi::dtype_ok(dtype), "bad dtype");
+    XC_REQ(batch >= 0 && heads > 0 && rows >= batch && max_len >= 1 && rows <= batch * max_len, "bad shape: every sample has 1 .. max_len rows");
+    XC_REQ(rows * heads < ((int64_t)1 << 31) && rows * 3 * heads * head_dim < ((int64_t)1 << 40), "too many rows");
+    XC_REQ(head_dim == 64 || head_dim == 128, "head_dim must be 64 or 128 (narrower / in-between widths are zero-padded by the caller)");
+    XC_REQ(ptrs_ok && cu != nullptr, "pointers must be non-null and 16-byte aligned");
+    XC_REQ(scale > 0.f, "scale must be positive");
+    memset(&p, 0, sizeof(p));
+    p.qkv = qkv; p.cu = cu; p.rows = (int)rows; p.batch = (int)batch; p.heads = (int)heads; p.max_len = (int)max_len; p.scale = scale;
+    return 0;
+#undef XC_REQ
+}
+static inline bool attn_varlen_resident(int dtype, int64_t head_dim, int64_t max_len) {
+    return dtype == XCLIP_BF16 && head_dim == 64 && max_len <= xc::A3_MAX_N;
+}
+template <typename T>
+static void launch_attn_varlen_plain(const xc::AttnVarlenParams& p, int64_t head_dim, bool backward, hipStream_t st) {
+    const dim3 grid((unsigned)(((int64_t)p.rows * p.heads + 3) / 4)), block(256);
+    if (head_dim == 64) {
+        if (backward) hipLaunchKernelGGL((xc::attn_varlen_plain_bwd_kernel<T, 64>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((xc::attn_varlen_plain_fwd_kernel<T, 64>), grid, block, 0, st, p);
+    } else {
+        if (backward) hipLaunchKernelGGL((xc::attn_varlen_plain_bwd_kernel<T, 128>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((xc::attn_varlen_plain_fwd_kernel<T, 128>), grid, block, 0, st, p);
+    }
+}
+
+extern "C" {
+
+int xclip_attention_varlen_fwd(const void* qkv, const int32_t* cu, void* out, float* lse, int64_t rows, int64_t batch, int64_t heads,
+                               int64_t head_dim, int64_t max_len, float scale, int dtype, void* stream) {
+    AttnVarlenParams p;
+    const int rc = attn_varlen_setup(__func__, qkv, cu, rows, batch, heads, head_dim, max_len, scale, dtype,
+                                     qkv && out && lse && aligned16(qkv) && aligned16(out), p);
+    if (rc != 0 || batch == 0) return rc;
+    p.out = out; p.lse = lse;
+    hipStream_t st = (hipStream_t)stream;
+    if (attn_varlen_resident(dtype, head_dim, max_len)) {
+        const int lds = attn_varlen_fwd_lds_bytes((int)max_len);
+        XC_REQUIRE(lds <= 160 * 1024, "internal: varlen forward LDS");
+        XC_ALLOW_LDS(attn_varlen_fwd_kernel, 160 * 1024);
+        hipLaunchKernelGGL(attn_varlen_fwd_kernel, dim3((unsigned)(batch * heads)), dim3(attn_varlen_fwd_waves((int)max_len) * 64), lds, st, p);
+    } else {
+        by_dtype(dtype, [&](auto t) { launch_attn_varlen_plain<typename decltype(t)::type>(p, head_dim, false, st); });
+    }
+    return check_launch(__func__);
+}
+
+int xclip_attention_varlen_bwd(const void* qkv, const int32_t* cu, const void* out, const void* dout, const float* lse, void* dqkv,
+                               int64_t rows, int64_t batch, int64_t heads, int64_t head_dim, int64_t max_len, float scale, int dtype,
+                               void* stream) {
+    AttnVarlenParams p;
+    const int rc = attn_varlen_setup(__func__, qkv, cu, rows, batch, heads, head_dim, max_len, scale, dtype,
+                                     qkv && out && dout && lse && dqkv && aligned16(qkv) && aligned16(out) && aligned16(dout) && aligned16(dqkv), p);
+    if (rc != 0 || batch == 0) return rc;
+    p.out = const_cast<void*>(out); p.lse = const_cast<float*>(lse); p.dout = dout; p.dqkv = dqkv;
+    hipStream_t st = (hipStream_t)stream;
+    if (attn_varlen_resident(dtype, head_dim, max_len)) {
+        const int lds = attn_varlen_bwd_lds_bytes((int)max_len);
+        XC_REQUIRE(lds <= 160 * 1024, "internal: varlen backward LDS");
+        XC_ALLOW_LDS(attn_varlen_bwd_kernel, 160 * 1024);
+        hipLaunchKernelGGL(attn_varlen_bwd_kernel, dim3((unsigned)(batch * heads)), dim3(attn_varlen_bwd_waves((int)max_len) * 64), lds, st, p);
+    } else {
+        by_dtype(dtype, [&](auto t) { launch_attn_varlen_plain<typename decltype(t)::type>(p, head_dim, true, st); });
+    }
     return check_launch(__func__);
 }
 

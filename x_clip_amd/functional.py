@@ -190,7 +190,10 @@ class _GainGrads:
 
 # ---- one pre-norm residual block pair (x_clip.py:285-289): the attention block and the feed-forward block -----------------------------
 # c: what a pass shares; seed: the layer's dropout seed (+ 1: the feed-forward block's); need / dg: the layer's `need` flags / gain accumulators
-_Pass = NamedTuple("_Pass", [("spec", StackSpec), ("B", int), ("n", int), ("mask", Optional[Tensor])])
+# layout (packing.TextLayout, or None): the rows are the kept rows of a padded batch laid end to end -- M = layout.R instead of B n; the
+# attention takes the samples' row ranges from layout.cu (attention_varlen.h), everything row-wise runs on the R rows unchanged
+_Pass = NamedTuple("_Pass", [("spec", StackSpec), ("B", int), ("n", int), ("mask", Optional[Tensor]), ("layout", object)])
+_Pass.__new__.__defaults__ = (None,)
 
 
 def _attn_forward(h: Tensor, W: LayerWeights, c: _Pass, seed: int):
@@ -198,6 +201,9 @@ def _attn_forward(h: Tensor, W: LayerWeights, c: _Pass, seed: int):
     M, D = h.shape
     spec, inner = c.spec, c.spec.inner
     qkv = ops.gemm(h, W.w_qkv, M, 3 * inner, D)                                        # to_qkv            :216
+    if c.layout is not None:                                   # samples of different lengths, end to end: no mask, no rotary, no dropout (text_encode_packed)
+        o, lse = ops.attention_varlen_fwd(qkv, c.layout.cu, c.layout.max_len, spec.heads, spec.scale, spec.head_slot)
+        return qkv, o, lse
     if spec.rotary is not None:
         ops.rotary_(qkv, c.n, spec.rotary, head_dim=spec.head_slot)                    # q, k, v rotated   :221-223
     o, lse = ops.attention_fwd(qkv.view(c.B, c.n, 3 * inner), c.mask, spec.heads, spec.scale, spec.causal, spec.head_slot, spec.attn_dropout, seed)   # :217-244
@@ -253,6 +259,8 @@ def _ffn_backward(dx2: Tensor, t: LayerTape, W: LayerWeights, need: LayerWeights
 def _attn_backward(do: Tensor, t: LayerTape, c: _Pass, seed: int) -> Tensor:
     """the dense attention: gradient w.r.t. its output [M, inner] -> gradient w.r.t. the packed rotated qkv [M, 3 inner]"""
     spec, B, n, inner = c.spec, c.B, c.n, c.spec.inner
+    if c.layout is not None:
+        return ops.attention_varlen_bwd(t.qkv, c.layout.cu, c.layout.max_len, t.o, do, t.lse, spec.heads, spec.scale, spec.head_slot)
     dqkv = ops.attention_bwd(t.qkv.view(B, n, 3 * inner), c.mask, t.o, do.view(B, n, inner), t.lse, spec.heads, spec.scale, spec.causal, spec.head_slot, spec.attn_dropout, seed)
     return dqkv.view(B * n, 3 * inner)
 
@@ -375,16 +383,18 @@ def can_pool(spec: StackSpec) -> bool:
 
 
 def stack_forward(x0: Tensor, B: int, n: int, spec: StackSpec, params: Sequence[Tensor], mask: Optional[Tensor],
-                  out: Optional[Tensor] = None, out_group: int = 0, keep_tape: bool = True, pool_row: Optional[int] = None):
+                  out: Optional[Tensor] = None, out_group: int = 0, keep_tape: bool = True, pool_row: Optional[int] = None, layout=None):
     """x0 [B*n, D] -> norm_out(...) [B*n, D] (or written into `out`, see ops.layernorm_fwd) and the backward tape.
-    pool_row = r: only token row r of every sample is wanted -> [B, D] (the last layer's row-wise part runs on those rows alone)"""
+    pool_row = r: only token row r of every sample is wanted -> [B, D] (the last layer's row-wise part runs on those rows alone).
+    layout (packing.TextLayout): x0 is [R, D], the kept rows end to end (_Pass); every layer runs on all R rows, no pooled last layer"""
     assert len(params) == 2 + LAYER_PARAMS * spec.depth
     assert pool_row is None or (can_pool(spec) and out is None and 0 <= pool_row < n)
+    assert layout is None or (pool_row is None and mask is None and out is None and x0.shape[0] == layout.R)
     x, m_in, r_in = ops.layernorm_fwd(x0, params[0])
     # dropout: one 64-bit seed per pass from torch's CPU generator (no device sync; torch.manual_seed makes it reproducible); layer l
     # uses seed + 2 l (attention) and seed + 2 l + 1 (feed-forward); the backward and a checkpointed re-run regenerate the same masks
     seed0 = _draw_seed() if (spec.attn_dropout > 0.0 or spec.ff_dropout > 0.0) else 0
-    layers, c = [], _Pass(spec, B, n, mask)
+    layers, c = [], _Pass(spec, B, n, mask, layout)
     for l in range(spec.depth):
         W, _ = layer_weights(params, l)
         if pool_row is not None and l == spec.depth - 1:
@@ -397,12 +407,13 @@ def stack_forward(x0: Tensor, B: int, n: int, spec: StackSpec, params: Sequence[
     return y, (x0, m_in, r_in, layers, x, m_out, r_out, seed0, pool_row) if keep_tape else None
 
 
-def stack_backward(dy: Tensor, tape, B: int, n: int, spec: StackSpec, params: Sequence[Tensor], mask: Optional[Tensor], need: Sequence[bool]):
-    """dy [B*n, D] contiguous ([B, D] for a pooled forward) -> (dx0, grads aligned with `params` (None where not needed))"""
+def stack_backward(dy: Tensor, tape, B: int, n: int, spec: StackSpec, params: Sequence[Tensor], mask: Optional[Tensor], need: Sequence[bool],
+                   layout=None):
+    """dy [B*n, D] contiguous ([B, D] for a pooled forward; [R, D] with the forward's `layout`) -> (dx0, grads aligned with `params` (None where not needed))"""
     x0, m_in, r_in, layers, x_last, m_out, r_out, seed0, pool_row = tape
     gg = _GainGrads(params, (True,) + spec.depth * IS_GAIN + (True,))
     grads: List[Optional[Tensor]] = [None] * len(params)
-    sg, c = _SideGemm(dy.device), _Pass(spec, B, n, mask)
+    sg, c = _SideGemm(dy.device), _Pass(spec, B, n, mask, layout)
     def stats_for(l: int):
         """the row constants of layer l's fused feed-forward backward can be written by the kernel that produces its output gradient -- the LayerNorm
         backward of the layer above it, or of norm_out -- whose input row is layer l's output.  Not with recompute (layer l's tape does not exist yet at that
@@ -547,6 +558,59 @@ def text_encode(tokens: Tensor, mask: Optional[Tensor], E: Tensor, P: Optional[T
     if pool_row is not None and not can_pool(spec):                   # (dropout: dense last layer, then the row)
         return select_row(_TextEncodeFn.apply(spec, tokens, mask, torch.is_grad_enabled(), None, E, P, cls, *stack), pool_row)
     return _TextEncodeFn.apply(spec, tokens, mask, torch.is_grad_enabled(), pool_row, E, P, cls, *stack)
+
+
+class _PackedTextEncodeFn(torch.autograd.Function):
+    """the text encoder on the kept rows alone (packing.TextLayout) -> the CLS row of every sample [b, D].  Padded rows are never embedded,
+    normalised, multiplied or attended from, forward or backward; no [b (n + 1), D] array is allocated on this path."""
+
+    @staticmethod
+    def forward(ctx, spec: StackSpec, layout, grad_mode: bool, E: Tensor, P: Optional[Tensor], cls: Tensor, *stack: Tensor):
+        keep = grad_mode and any(ctx.needs_input_grad)
+        x0 = ops.text_embed_packed_fwd(layout.tok, layout.pos, E, P, cls)                # token_emb + pos, the cls rows   :320-331
+        y, tape = stack_forward(x0, layout.batch, layout.max_len, spec, stack, None, keep_tape=keep, layout=layout)
+        ctx.save_for_backward(*stack)
+        ctx.spec, ctx.layout, ctx.tape = spec, layout, tape
+        ctx.meta = (E.shape[0], E.shape[1], 0 if P is None else P.shape[0], E.dtype)
+        return ops.gather_rows(y, layout.cu[:-1])                                        # enc_text[:, 0]                  :708
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        vocab, D, npos, dtype = ctx.meta
+        lay = ctx.layout
+        need = ctx.needs_input_grad[3:]
+        dy = _contig_grad(dy, (lay.batch, D), dtype, lay.cu.device)
+        # dy into the CLS rows of a zeroed [R, D]: as a gather, row r takes dy[s] where r = cu[s] and the appended zero row elsewhere
+        src = torch.full((lay.R,), lay.batch, dtype=torch.int32, device=dy.device)
+        src[lay.cu[:-1].long()] = torch.arange(lay.batch, dtype=torch.int32, device=dy.device)
+        dyr = ops.gather_rows(torch.cat([dy, dy.new_zeros(1, D)], dim=0), src)
+        dx0, sgrads = stack_backward(dyr, _take_tape(ctx), lay.batch, lay.max_len, ctx.spec, ctx.saved_tensors, None, need[3:], layout=lay)
+        dE = dP = dcls = None
+        if need[0] or need[1] or need[2]:
+            tok_key, pos_key = lay.keys(vocab, npos)
+            aE, aP, acls = ops.text_embed_packed_bwd(dx0, tok_key, pos_key, lay.cu, vocab, npos, True, need_E=need[0], need_P=need[1])
+            dE = ops.cast_from_f32(aE, dtype) if need[0] else None
+            dP = ops.cast_from_f32(aP, dtype) if (need[1] and aP is not None) else None
+            dcls = ops.cast_from_f32(acls, dtype) if need[2] else None
+        return (None, None, None, dE, dP, dcls, *sgrads)
+
+
+def text_encode_packed(layout, E: Tensor, P: Optional[Tensor], cls: Optional[Tensor], stack: Sequence[Tensor], spec: StackSpec) -> Tensor:
+    """TextTransformer.forward (x_clip.py:317-338) followed by `[:, 0]` (x_clip.py:708) for a packed batch -> [b, D]: the same function of
+    the same tokens as text_encode(..., mask, pool_row=0), computed on the kept rows only.  Every layer runs on all R rows (there is no
+    varlen one-query attention: the dense path's pooled last layer has no packed twin)."""
+    if cls is None:
+        raise NotImplementedError("pack_text: the packed text tower returns the CLS row (text_has_cls_token=True)")
+    if spec.rotary is not None or spec.causal or spec.attn_dropout > 0.0 or spec.ff_dropout > 0.0:
+        raise NotImplementedError("pack_text: no rotary embedding (text_rotary_pos_emb), causal mask (text_causal_mask) or dropout in the packed text tower")
+    if not layout.has_cls or layout.R < layout.batch:
+        raise ValueError("pack_text: the layout must keep a CLS row per sample (text_layout(..., has_cls=True))")
+    if P is not None and layout.n > P.shape[0]:
+        raise IndexError(f"text length {layout.n} exceeds max_seq_len {P.shape[0]}")
+    if layout.cu.device != E.device:
+        layout = layout.to(E.device)
+    return _PackedTextEncodeFn.apply(spec, layout, torch.is_grad_enabled(), E, P, cls, *stack)
 
 
 # ---- vision encoder -----------------------------------------------------------------------------------------------------------

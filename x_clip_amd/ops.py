@@ -355,6 +355,46 @@ def text_embed_bwd(dout: Tensor, tokens: Tensor, vocab: int, has_pos: bool, has_
     return dE, dP, dcls
 
 
+def text_embed_packed_fwd(tok: Tensor, pos: Tensor, E: Tensor, P: Optional[Tensor], cls: Optional[Tensor]) -> Tensor:
+    """the embedding of the kept rows of a packed batch (packing.TextLayout): tok int64 [R], pos int32 [R] (0 = the CLS row when cls is given)
+    -> [R, D]; bit-equal to those rows of text_embed_fwd"""
+    _dev_check(tok, pos, E, P, cls)
+    assert tok.dtype == torch.int64 and pos.dtype == torch.int32 and tok.dim() == 1 and tok.shape == pos.shape
+    tok, pos = _c(tok), _c(pos)
+    vocab, dim = E.shape
+    out = torch.empty(tok.numel(), dim, dtype=E.dtype, device=E.device)
+    tf = _TokenFlag.get(E.device)
+    tf.poll(vocab)
+    _lib.check(_lib.lib().xclip_text_embed_packed_fwd(tok.data_ptr(), pos.data_ptr(), _c(E).data_ptr(), _ptr(None if P is None else _c(P)),
+                                                      _ptr(None if cls is None else _c(cls)), out.data_ptr(), tok.numel(), dim, vocab,
+                                                      0 if P is None else P.shape[0], tf.flag.data_ptr(), dtype_code(E), _stream(E)),
+               "xclip_text_embed_packed_fwd")
+    tf.after_launch(vocab)
+    return out
+
+
+def text_embed_packed_bwd(dout: Tensor, tok_key: Tensor, pos_key: Tensor, cu: Tensor, vocab: int, npos: int, has_cls: bool,
+                          need_E: bool = True, need_P: bool = True):
+    """dout [R, D] -> fp32 accumulators dE [vocab, D] | None, dP [npos, D] | None (npos = 0: no table), dcls [D] | None.  tok_key / pos_key int64
+    [R]: the row's token id / table position, with `vocab` / `npos` on the CLS rows (an id past the table: dropped by the segmented sum)"""
+    _dev_check(dout, tok_key, pos_key, cu)
+    dout = _c(dout)
+    R, dim = dout.shape
+    _TokenFlag.get(dout.device).poll(vocab)
+    dE = dP = dcls = None
+    if need_E:
+        dE = torch.zeros(vocab, dim, dtype=torch.float32, device=dout.device)
+        scatter_add_sorted(dout, *sort_ids(tok_key, vocab + 1), dE)
+    if need_P and npos > 0:
+        dP = torch.zeros(npos, dim, dtype=torch.float32, device=dout.device)
+        scatter_add_sorted(dout, *sort_ids(pos_key, npos + 1), dP)
+    if has_cls:
+        dcls = torch.zeros(dim, dtype=torch.float32, device=dout.device)
+        _lib.check(_lib.lib().xclip_text_embed_packed_bwd(dout.data_ptr(), cu.data_ptr(), dcls.data_ptr(), cu.numel() - 1, dim, dtype_code(dout),
+                                                          _stream(dout)), "xclip_text_embed_packed_bwd")
+    return dE, dP, dcls
+
+
 def sort_ids(ids: Tensor, id_limit: int) -> Tuple[Tensor, Tensor]:
     """(ids ascending, perm) of a flat int64 id vector with values in [0, id_limit): perm[e] = where entry e stood; stable.  What
     `scatter_add_sorted` wants in front of it (the nn.Embedding backward of x_clip.py:320 as a segmented sum); sort.h's radix passes"""
@@ -694,6 +734,44 @@ def attention_bwd(qkv: Tensor, mask: Optional[Tensor], out: Tensor, dout: Tensor
                                               int(dropout_seed) & _U64, dtype_code(qkv), _stream(qkv)), "xclip_attention_bwd")
     if probe is not None:      # dV = P^T dO, dP = dO V^T, dQ = dS K, dK = dS^T Q (algorithmic: 4 products; the S recompute is the implementation's); q, k, v, o, dO in, dq, dk, dv out
         probe.end(qkv, ev0, "attention", 8.0 * b * heads * n * n * head_dim, 8 * b * n * heads * head_dim * qkv.element_size() + 8 * b * heads * n, "attn_bwd")
+    return dqkv
+
+
+def attention_varlen_fwd(qkv: Tensor, cu: Tensor, max_len: int, heads: int, scale: float, head_dim: int = 64) -> Tuple[Tensor, Tensor]:
+    """samples of different lengths laid end to end: qkv [R, 3*heads*head_dim], cu int32 [b + 1] (sample s = rows cu[s] .. cu[s+1], each
+    1 .. max_len long); every key of a sample visible to every query of that sample and to no other -> out [R, heads*head_dim], lse fp32 [heads, R]"""
+    _dev_check(qkv, cu)
+    qkv = _c(qkv)
+    R, w = qkv.shape
+    assert head_dim in (64, 128) and w == 3 * heads * head_dim, "x_clip_amd attention kernels hold head slots of 64 or 128 features"
+    assert cu.dtype == torch.int32 and cu.dim() == 1 and cu.is_contiguous() and cu.numel() >= 1
+    out = torch.empty(R, heads * head_dim, dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty(heads, R, dtype=torch.float32, device=qkv.device)
+    probe = _probe(qkv)
+    ev0 = probe.begin(qkv) if probe is not None else None
+    _lib.check(_lib.lib().xclip_attention_varlen_fwd(qkv.data_ptr(), cu.data_ptr(), out.data_ptr(), lse.data_ptr(), R, cu.numel() - 1, heads, head_dim,
+                                                     int(max_len), scale, dtype_code(qkv), _stream(qkv)), "xclip_attention_varlen_fwd")
+    if probe is not None:      # (the flop count needs the lengths, which live on the device: bytes only -- q, k, v in, o out)
+        probe.end(qkv, ev0, "attention", 0.0, 4 * R * heads * head_dim * qkv.element_size() + 4 * heads * R, "attn_varlen_fwd")
+    return out, lse
+
+
+def attention_varlen_bwd(qkv: Tensor, cu: Tensor, max_len: int, out: Tensor, dout: Tensor, lse: Tensor, heads: int, scale: float,
+                         head_dim: int = 64) -> Tensor:
+    """-> dqkv [R, 3*heads*head_dim], every row written"""
+    _dev_check(qkv, cu, out, dout, lse)
+    qkv, out, dout = _c(qkv), _c(out), _c(dout)
+    R = qkv.shape[0]
+    assert tuple(out.shape) == (R, heads * head_dim) and out.shape == dout.shape and dout.dtype == qkv.dtype
+    assert lse.dtype == torch.float32 and lse.is_contiguous() and tuple(lse.shape) == (heads, R) and cu.dtype == torch.int32 and cu.is_contiguous()
+    dqkv = torch.empty_like(qkv)
+    probe = _probe(qkv)
+    ev0 = probe.begin(qkv) if probe is not None else None
+    _lib.check(_lib.lib().xclip_attention_varlen_bwd(qkv.data_ptr(), cu.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), dqkv.data_ptr(), R,
+                                                     cu.numel() - 1, heads, head_dim, int(max_len), scale, dtype_code(qkv), _stream(qkv)),
+               "xclip_attention_varlen_bwd")
+    if probe is not None:      # q, k, v, o, dO in, dq, dk, dv out
+        probe.end(qkv, ev0, "attention", 0.0, 8 * R * heads * head_dim * qkv.element_size() + 8 * heads * R, "attn_varlen_bwd")
     return dqkv
 
 
