@@ -78,7 +78,7 @@ int xclip_text_embed_bwd(const void* dout, const int64_t* tokens, float* dE_accu
 /* The same embedding for a PACKED batch (x_clip.py:320-331 restricted to the rows the key-padding mask of x_clip.py:614,334 keeps): `rows`
  * kept rows laid end to end, sample s in rows cu[s] .. cu[s+1].  tok [rows] int64 = the row's token id (ignored on CLS rows), pos [rows] int32 =
  * its position inside its sample, position 0 being the CLS row when cls != NULL:  out[r] = cls if cls && pos[r] == 0, else
- * E[tok[r]] + P[pos[r] - (cls != NULL)] (P may be NULL; it has `npos` rows).  Ids outside [0, vocab) and positions outside the table give a
+ * E[tok[r]] + P[pos[r] - (cls != NULL)] (P may be NULL; it has `npos` rows).  Ids outside [0, vocab) and, with a table, positions outside it give a
  * NaN row and set *bad_token_flag, as above.  Bit-equal to the kept rows of xclip_text_embed_fwd.
  * Backward: dcls_accum [dim] fp32 += the column sum of dout over the CLS rows cu[0 .. batch) (a model with a CLS row).  dE and dP are segmented
  * sums: xclip_sort_ids on the packed ids / positions, then xclip_scatter_add_sorted (n_in = n_out = 1) -- no [batch, n + 1, dim] array. */

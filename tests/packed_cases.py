@@ -102,11 +102,15 @@ def check_varlen(got, want, dtype, tag):
     K.close(dqkv, r_grad, dtype, f"varlen attn dqkv {tag}", mult=3.0, ulps=2.0, unit="scale")
 
 
-def case_varlen_attention(dev, dtype, lens, heads, slot, dim_head, seed=0):
+def case_varlen_attention(dev, dtype, lens, heads, slot, dim_head, seed=0, max_len=None, tag=None):
+    """max_len = None: the longest sample's length, as text_layout counts it; larger: the launch sized for a sample the batch does not hold
+    (cat_layouts).  `tag` names the check in the parity report (a sweep keeps one line, the worst of its cases); -> (got, want)"""
     qkv, dout = varlen_data(lens, heads, slot, dim_head, dtype, dev, seed)
     scale = dim_head ** -0.5
-    got = varlen_launch(qkv, dout, _cu(lens, dev), max(lens), heads, slot, scale)
-    check_varlen(got, varlen_reference(qkv, dout, lens, heads, slot, scale), dtype, f"lens {lens[:4]}.. h{heads} slot{slot}/{dim_head}")
+    got = varlen_launch(qkv, dout, _cu(lens, dev), max(lens) if max_len is None else max_len, heads, slot, scale)
+    want = varlen_reference(qkv, dout, lens, heads, slot, scale)
+    check_varlen(got, want, dtype, tag or f"lens {lens[:4]}.. h{heads} slot{slot}/{dim_head}")
+    return got, want
 
 
 def case_varlen_equals_dense(dev, dtype, B, n, heads, slot):
@@ -136,40 +140,102 @@ def case_varlen_full(dev, dtype=BF16, samples=256, heads=8, slot=64, repeats=3):
 
 
 # ---- packed embedding ---------------------------------------------------------------------------------------------------------------------
-def embed_tokens(B=6, n=9, vocab=50):
-    g = torch.Generator().manual_seed(77)
+def embed_tokens(B=6, n=9, vocab=50, seed=77):
+    """the first six samples are one of each kind; the ones behind them have padded tails of every length"""
+    g = torch.Generator().manual_seed(seed)
     tok = torch.randint(1, vocab, (B, n), generator=g)
     tok[0, 5:] = 0                                              # a padded tail
-    tok[1] = 0                                                  # all padding: the CLS row alone
-    tok[2, 3] = 0                                               # a hole
-    tok[3, :4] = 7                                              # a repeated id (and again in another sample)
-    tok[4, 0] = 7
-    tok[4, 6:] = 0
-    return tok                                                  # (sample 5: full)
+    if B > 1:
+        tok[1] = 0                                              # all padding: the CLS row alone
+    if B > 2:
+        tok[2, 3] = 0                                           # a hole
+    if B > 3:
+        tok[3, :4] = 7                                          # a repeated id (and again in another sample)
+    if B > 4:
+        tok[4, 0] = 7
+        tok[4, 6:] = 0
+    for r in range(6, B):                                       # (sample 5: full)
+        tok[r, 1 + (r * 5) % n:] = 0
+    return tok
 
 
-def case_packed_embedding(dev, dtype, dim=64, vocab=50):
-    tok = embed_tokens(vocab=vocab)
-    B, n = tok.shape
-    E, P, cls = K.rnd((vocab, dim), dtype, 1).to(dev), K.rnd((n, dim), dtype, 2).to(dev), K.rnd((dim,), dtype, 3).to(dev)
-    lay = text_layout(tok, pad_id=0).to(dev)
-    keep = torch.cat([torch.ones(B, 1, dtype=torch.bool), tok != 0], dim=1).reshape(-1)
-    assert lay.R == int(keep.sum()) and lay.max_len == n + 1 and int(lay.cu[2] - lay.cu[1]) == 1
-    dense = ops.text_embed_fwd(tok.to(dev), E, P, cls).view(B * (n + 1), dim)
+def _segmented(keys, size, d64):
+    """fp64 index_add_ of the rows whose key lies inside the table -> (sum, k 2^-24 sum |terms|: the fp32-summation bound of k terms, as
+    cached_cases.case_accumulate derives it -- k roundings of at most half an fp32 ulp of a partial sum that never exceeds sum |terms|)"""
+    live = (keys >= 0) & (keys < size)
+    dim = d64.shape[1]
+    want = torch.zeros(size, dim, dtype=torch.float64).index_add_(0, keys[live], d64[live])
+    mag = torch.zeros(size, dim, dtype=torch.float64).index_add_(0, keys[live], d64[live].abs())
+    cnt = torch.zeros(size, dtype=torch.float64).index_add_(0, keys[live], torch.ones(int(live.sum()), dtype=torch.float64))
+    return want, cnt[:, None] * 2.0 ** -24 * mag
+
+
+def _within(name, dtype, got, want, bound, factor=1.0):
+    err = (got.detach().cpu().double() - want).abs()
+    ratio = float((err / bound.clamp_min(1e-300)).max())
+    K._record(f"packed embedding {name}", dtype, ratio, factor, "of k 2^-24 sum |terms|, element-wise")
+    assert bool((err <= factor * bound).all()), f"packed embedding {name}: worst error / bound {ratio:.3f} (allowed {factor})"
+
+
+def case_packed_embedding(dev, dtype, B=6, n=9, dim=64, vocab=50, has_pos=True, has_cls=True):
+    """forward: the bits of the kept rows of text_embed_fwd, and the bits of E[tok] + P[pos] formed in fp32 and rounded once (cls on the CLS
+    rows) -- which does not lean on the dense kernel.  backward: dE, dP, dcls against fp64 within the derived fp32-summation bound, and against
+    text_embed_bwd on the dense gradient that is zero on the dropped rows (two fp32 sums of the same terms: twice that bound; at the first
+    shape of this case also the 1e-6 of the scale it has always held)"""
+    tok = embed_tokens(B, n, vocab)
+    if not has_cls and B > 1:
+        with pytest.raises(ValueError, match="at least one kept token"):
+            text_layout(tok, pad_id=0, has_cls=False)            # sample 1 is all padding: without a CLS row it would own no row at all
+        tok[1, 2] = 3
+    c = int(has_cls)
+    E, P, cls = K.rnd((vocab, dim), dtype, 1), K.rnd((n, dim), dtype, 2) if has_pos else None, K.rnd((dim,), dtype, 3) if has_cls else None
+    E_d, P_d, cls_d = E.to(dev), None if P is None else P.to(dev), None if cls is None else cls.to(dev)
+    lay = text_layout(tok, pad_id=0, has_cls=has_cls).to(dev)
+    keep = (torch.cat([torch.ones(B, 1, dtype=torch.bool), tok != 0], dim=1) if has_cls else tok != 0)
+    assert lay.R == int(keep.sum()) and lay.max_len == int(keep.sum(1).max()) and lay.batch == B
+    if B > 5:
+        assert lay.max_len == n + c                              # sample 5 is full
+    if B > 1 and has_cls:
+        assert int(lay.cu[2] - lay.cu[1]) == 1
+    keep = keep.reshape(-1)
+    dense = ops.text_embed_fwd(tok.to(dev), E_d, P_d, cls_d).view(B * (n + c), dim)
     with C.poisoned_empty():
-        packed = ops.text_embed_packed_fwd(lay.tok, lay.pos, E, P, cls)
+        packed = ops.text_embed_packed_fwd(lay.tok, lay.pos, E_d, P_d, cls_d)
     assert torch.equal(packed, dense[keep.to(dev)]), "packed embedding forward is not bit-equal to the kept rows of text_embed_fwd"
+    tk, ps = lay.tok.cpu(), lay.pos.cpu().long()
+    want = E.float()[tk]
+    if has_pos:
+        want = want + P.float()[(ps - c).clamp_min(0)]
+    want = want.to(dtype)
+    if has_cls:
+        want[ps == 0] = cls
+        assert bool((ps[lay.cu[:-1].cpu().long()] == 0).all()) and int((ps == 0).sum()) == B
+    assert torch.equal(_bits(packed.cpu()), _bits(want)), "packed embedding forward is not E[tok] + P[pos] rounded once"
+
     d_packed = K.rnd((lay.R, dim), dtype, 4).to(dev)
-    d_dense = torch.zeros(B * (n + 1), dim, dtype=dtype, device=dev)
+    d_dense = torch.zeros(B * (n + c), dim, dtype=dtype, device=dev)
     d_dense[keep.to(dev)] = d_packed                             # a dense gradient that is zero on the dropped rows
     st = ops.sort_ids(tok.to(dev).reshape(-1), vocab)
-    wE, wP, wc = ops.text_embed_bwd(d_dense.view(B, n + 1, dim), tok.to(dev), vocab, True, True, sorted_tokens=st)
-    tk, pk = lay.keys(vocab, n)
-    gE, gP, gc = ops.text_embed_packed_bwd(d_packed, tk, pk, lay.cu, vocab, n, True)
-    for name, got, want in (("dE", gE, wE), ("dP", gP, wP), ("dcls", gc, wc)):
-        s = float(want.abs().max())
-        err = float((got - want).abs().max())
-        assert err <= 1e-6 * s, f"packed embedding {name}: {err:.3e} against scale {s:.3e}"
+    wE, wP, wc = ops.text_embed_bwd(d_dense.view(B, n + c, dim), tok.to(dev), vocab, has_pos, has_cls, sorted_tokens=st)
+    tkey, pkey = lay.keys(vocab, n)
+    gE, gP, gc = ops.text_embed_packed_bwd(d_packed, tkey, pkey, lay.cu, vocab, n if has_pos else 0, has_cls)
+    assert (gP is None) == (not has_pos) and (gc is None) == (not has_cls) and (wP is None) == (gP is None) and (wc is None) == (gc is None)
+    d64 = d_packed.cpu().double()
+    refs = {"dE": (gE, wE) + _segmented(tkey.cpu(), vocab, d64)}
+    if has_pos:
+        refs["dP"] = (gP, wP) + _segmented(pkey.cpu(), n, d64)
+    if has_cls:
+        first = d64[lay.cu[:-1].cpu().long()]
+        refs["dcls"] = (gc, wc, first.sum(0), B * 2.0 ** -24 * first.abs().sum(0))
+    tag = f"B{B} dim{dim}" + ("" if has_pos else " no pos") + ("" if has_cls else " no cls")
+    for name, (got, dense_got, ref, bound) in refs.items():
+        assert got.dtype == F32 and got.shape == ref.shape, name
+        _within(f"{name} vs fp64 {tag}", dtype, got, ref, bound)
+        _within(f"{name} vs text_embed_bwd {tag}", dtype, got, dense_got.detach().cpu().double(), bound, factor=2.0)
+        if B <= 6:
+            s = float(dense_got.abs().max())
+            err = float((got - dense_got).abs().max())
+            assert err <= 1e-6 * s, f"packed embedding {name}: {err:.3e} against scale {s:.3e}"
     assert float(gE[0].abs().max()) == 0.0                       # the pad id owns no kept row
 
 
@@ -219,10 +285,15 @@ WIDE = O.ClipConfig(dim_text=512, dim_image=512, dim_latent=512, num_text_tokens
                     visual_enc_depth=1, visual_image_size=64, visual_patch_size=32, visual_heads=8)
 
 
-def small_setup(variant, dtype, batch=None, seed=11, wide=False):
-    """batch 8 by default: every kind of sample (all padding, full, a hole, padded tails of five lengths) at an emulator time of seconds"""
+def small_setup(variant, dtype, batch=None, seed=11, wide=False, cfg=None, pad=None):
+    """batch 8 by default: every kind of sample (all padding, full, a hole, padded tails of five lengths) at an emulator time of seconds.
+    cfg / pad: another model (with the variant's loss) and another padding of its tokens"""
     v = VARIANTS[variant]
-    cfg = v["cfg"]
+    if cfg is not None:
+        cfg = O.ClipConfig(**dict(cfg.__dict__, decoupled_contrastive_learning=v["cfg"].decoupled_contrastive_learning))
+    else:
+        cfg = v["cfg"]
+    pad_text = padded_text if pad is None else pad
     if wide:
         cfg = O.ClipConfig(**dict(WIDE.__dict__, decoupled_contrastive_learning=cfg.decoupled_contrastive_learning))
     if batch is None:
@@ -234,12 +305,12 @@ def small_setup(variant, dtype, batch=None, seed=11, wide=False):
         extra["sigmoid_loss"] = True
     sd = {k: (t.to(dtype) if t.is_floating_point() else t) for k, t in sd.items()}
     text, image, aug_t, aug_i = O.make_inputs(cfg, batch, seed + 1, *v["aug"])
-    text, aug_t = padded_text(cfg, text), [padded_text(cfg, a.roll(1, 0)) for a in aug_t]
+    text, aug_t = pad_text(cfg, text), [pad_text(cfg, a.roll(1, 0)) for a in aug_t]
     return cfg, sd, extra, text, image.to(dtype), aug_t, [a.to(dtype) for a in aug_i]
 
 
-def run_model(dev, dtype, variant, pack, layout_from=None, batch=None, wide=False, **ctor):
-    cfg, sd, extra, text, image, aug_t, aug_i = small_setup(variant, dtype, batch, wide=wide)
+def run_model(dev, dtype, variant, pack, layout_from=None, batch=None, wide=False, cfg=None, pad=None, **ctor):
+    cfg, sd, extra, text, image, aug_t, aug_i = small_setup(variant, dtype, batch, wide=wide, cfg=cfg, pad=pad)
     model = C.build_clip(cfg, {k: t.float() for k, t in sd.items()}, dev, dtype, **extra, **ctor)
     if pack is not None:
         model.pack_text = pack
@@ -253,8 +324,8 @@ def run_model(dev, dtype, variant, pack, layout_from=None, batch=None, wide=Fals
     return model, loss.detach(), {k: p.grad for k, p in model.named_parameters()}
 
 
-def oracle(variant, dtype, batch=None, wide=False):
-    cfg, sd, _, text, image, aug_t, aug_i = small_setup(variant, dtype, batch, wide=wide)
+def oracle(variant, dtype, batch=None, wide=False, cfg=None, pad=None):
+    cfg, sd, _, text, image, aug_t, aug_i = small_setup(variant, dtype, batch, wide=wide, cfg=cfg, pad=pad)
     sd64 = {k: (t.double().clone().requires_grad_(True) if t.is_floating_point() else t) for k, t in sd.items()}
     with O.layer_norm_eps(1e-5 if dtype == F32 else 1e-3):
         if VARIANTS[variant]["sigmoid"]:
@@ -270,15 +341,17 @@ def oracle(variant, dtype, batch=None, wide=False):
 _ORACLE = {}
 
 
-def case_vs_oracle(dev, dtype, variant):
+def case_vs_oracle(dev, dtype, variant, cfg=None, pad=None):
     """pack_text = True against the fp64 oracle on the same (dtype-rounded) parameters and padded tokens; the pad id's embedding gradient is exactly zero.
-    bf16 runs the dim-512 model the bf16 bars are stated for (WIDE above), fp32 the two-layer CFG1"""
-    wide = dtype != F32
-    key = (variant, dtype)
+    bf16 runs the dim-512 model the bf16 bars are stated for (WIDE above), fp32 the two-layer CFG1 -- or the model `cfg` with its tokens padded
+    by `pad` (packed_sweep_cases.case_vs_oracle_mid)"""
+    wide = dtype != F32 and cfg is None
+    setup = dict(wide=wide, cfg=cfg, pad=pad)
+    key = (variant, dtype, repr(cfg), getattr(pad, "__name__", None))
     if key not in _ORACLE:
-        _ORACLE[key] = oracle(variant, dtype, wide=wide)
+        _ORACLE[key] = oracle(variant, dtype, **setup)
     ref_loss, ref_grads = _ORACLE[key]
-    model, loss, grads = run_model(dev, dtype, variant, True, wide=wide)
+    model, loss, grads = run_model(dev, dtype, variant, True, **setup)
     fp32 = dtype == F32
     err = abs(float(loss) - ref_loss) / max(1.0, abs(ref_loss))
     print(f"packed {variant} {dtype}: loss err {err:.2e}")
@@ -294,7 +367,7 @@ def case_vs_oracle(dev, dtype, variant):
         cos = float((g * rg).sum() / (g.norm() * rg.norm()))
         print(f"packed {variant} {dtype} {k}: rel {rel:.2e} cos {cos:.6f}")
         assert (rel < 3e-4) if fp32 else (rel < 0.08 and cos > 0.999), (k, rel, cos)
-    pad_row = grads["text_transformer.token_emb.weight"][O.CFG1.text_pad_id]
+    pad_row = grads["text_transformer.token_emb.weight"][(cfg or O.CFG1).text_pad_id]
     assert float(pad_row.abs().max()) == 0.0, "the pad id's embedding row received a gradient"
 
 

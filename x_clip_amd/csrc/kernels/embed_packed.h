@@ -24,7 +24,8 @@ __global__ __launch_bounds__(256) void text_embed_packed_fwd_kernel(const long l
     const int j = pos[row] - has_cls;                          // token position; -1 on the CLS row
     const int nch = D / VEC;
     long long id = (j < 0) ? 0 : tok[row];
-    const bool bad = id < 0 || id >= vocab || j >= npos;       // (wave-uniform; a position past the table is a malformed layout)
+    // (wave-uniform; a position past the table is a malformed layout -- where there is a table: without one npos is 0 and no position is read)
+    const bool bad = id < 0 || id >= vocab || (P != nullptr && j >= npos);
     if (bad) {
         id = 0;
         if (lane == 0 && bad_flag != nullptr) *bad_flag = 1;
