@@ -20,7 +20,7 @@ extern "C" {
 #endif
 
 enum { XCLIP_F32 = 0, XCLIP_BF16 = 1 };
-#define XCLIP_ABI_VERSION 31
+#define XCLIP_ABI_VERSION 32
 
 int xclip_abi_version(void);
 const char* xclip_last_error(void);
@@ -242,7 +242,22 @@ int xclip_attention_varlen_fwd(const void* qkv, const int32_t* cu, void* out, fl
 int xclip_attention_varlen_bwd(const void* qkv, const int32_t* cu, const void* out, const void* dout, const float* lse, void* dqkv,
                                int64_t rows, int64_t batch, int64_t heads, int64_t head_dim, int64_t max_len, float scale, int dtype,
                                void* stream);
-/* Feed-forward dropout (nn.Dropout between the inner LayerNorm and the second Linear, x_clip.py:193-194): y[i] = x[i] keep(i) / (1 - p)
+/* The one-query attention over samples of DIFFERENT lengths laid end to end -- the last layer of the packed text tower under the CLS head
+ * (x_clip.py:708 `enc_text[:, 0]`; Attention.forward x_clip.py:213-245 restricted to that query, under the key-padding mask of x_clip.py:334 on
+ * the kept rows only):
+ * q [batch, heads, head_dim] = to_qkv's first third applied to the first row of every sample; kv [rows, 2, heads, head_dim] = its other two
+ * thirds for every kept row; cu [batch + 1] int32 ascending: sample s owns rows cu[s] .. cu[s+1] (a range is cut to [0, rows]).  Every key of a
+ * sample is visible to its query and to no other: no mask, no causal flag, no dropout.  scale > 0.
+ * out [batch, heads, head_dim]; lse [batch, heads] fp32 (natural log of the scaled scores' sum), saved for the backward.
+ * Backward: dq [batch, heads, head_dim] and dkv [rows, 2, heads, head_dim]; every row a sample owns is written exactly once, nothing at or
+ * beyond row `rows` is read or written; no atomics, a fixed summation order.  A sample of length 0 gets out = 0, lse = 0, dq = 0 and no dkv
+ * row (the "no visible key" convention above). */
+int xclip_attention_pool_varlen_fwd(const void* q, const void* kv, const int32_t* cu, void* out, float* lse, int64_t rows, int64_t batch,
+                                    int64_t heads, int64_t head_dim, float scale, int dtype, void* stream);
+int xclip_attention_pool_varlen_bwd(const void* q, const void* kv, const int32_t* cu, const void* out, const void* dout, const float* lse,
+                                    void* dq, void* dkv, int64_t rows, int64_t batch, int64_t heads, int64_t head_dim, float scale, int dtype,
+                                    void* stream);
+/* Feed-forward dropout(nn.Dropout between the inner LayerNorm and the second Linear, x_clip.py:193-194): y[i] = x[i] keep(i) / (1 - p)
  * over n contiguous elements (n a multiple of the 16-byte chunk), keep(i) iff drop_hash(seed, i) >= p 2^32.  The same call on the
  * gradient is the backward; y == x is allowed. */
 int xclip_dropout(const void* x, void* y, int64_t n, float p, uint64_t seed, int dtype, void* stream);
@@ -382,8 +397,12 @@ int xclip_rowgrad(const float* S, int64_t lds, const float* lse, int64_t rows, i
  * cross_entropy_fwd: lse[r] = log sum_{c < cols} exp(x[r, c]); *loss_accum += sum_r (lse[r] - x[r, labels[r]]) (the caller
  *   divides by the number of rows: F.cross_entropy(..., ignore_index) averages over the non-ignored positions).
  * cross_entropy_bwd: in place, x[r, c] <- (*gmul / rows) (softmax(x[r])[c] - [c == labels[r]]) for c < cols, 0 in the padding
- *   columns [cols, ld). */
+ *   columns [cols, ld).
+ * rows_add_at: dst[idx[r], :] = round(fp32(dst[idx[r], :]) + fp32(src[r, :])) for src [rows, dim] contiguous and dst with row stride ldd --
+ *   the gather's transpose onto rows that hold a value already.  idx int32, STRICTLY ascending (distinct rows: one writer per element, no
+ *   atomics); the packed text tower adds the CLS rows' gradients (`enc_text[:, 0]`, x_clip.py:708) into the [rows, dim] gradient with it. */
 int xclip_gather_rows(const void* src, int64_t lds, const int32_t* idx, void* out, int64_t rows, int64_t dim, int dtype, void* stream);
+int xclip_rows_add_at(void* dst, int64_t ldd, const int32_t* idx, const void* src, int64_t rows, int64_t dim, int dtype, void* stream);
 int xclip_cross_entropy_fwd(const void* logits, int64_t ld, const int64_t* labels, int64_t rows, int64_t cols, float* lse, float* loss_accum,
                             int dtype, void* stream);
 int xclip_cross_entropy_bwd(void* logits, int64_t ld, const int64_t* labels, const float* lse, const float* gmul, int64_t rows, int64_t cols,

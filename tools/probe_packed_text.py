@@ -3,9 +3,11 @@
     python tools/probe_packed_text.py [--batch 1024] [--rounds 6] > profiles/rNN_packed_text_probe.log
 
 Token lengths are drawn with a fixed seed, uniform in [1, 2 f n], so that the fill R / (b (n + 1)) is about f = 1/16, 1/4 and 1 of n = 256 (f = 1:
-no padding at all).  At each fill the step is timed with `pack_text` off (today's pruned path) and on, ALTERNATING in one session (off, on, off,
-on, ...: drift of the clocks hits both alike); reported: the median step of each, their ratio, the peak of reserved memory of each mode (measured in
-a pass of its own after emptying the cache), and the varlen attention forward / backward alone on the layout of that fill."""
+no padding at all).  At each fill the step is timed in three modes -- `pack_text` off (the pruned dense path), on, and on with
+`pack_text_pool_last` -- ALTERNATING in one session (off, on, pool, off, on, pool, ...: drift of the clocks hits all alike); reported: the median
+step of each, the ratios to off, the peak of reserved memory of each mode (measured in a pass of its own after emptying the cache), and per layer
+on the layout of that fill the varlen attention forward / backward and the one-query varlen attention forward / backward (8 heads); at fill 1 also
+the dense one-query kernels (attn_pool_*) on the same rows viewed as [b, n + 1], for comparison."""
 import argparse
 import os
 import statistics
@@ -15,6 +17,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from x_clip_amd import CLIP, ops, text_layout  # noqa: E402
+
+MODES = ("off", "on", "pool")
 
 
 def timed(fn, dev):
@@ -38,8 +42,11 @@ def main():
     n, b = model.text_seq_len, args.batch
     g = torch.Generator().manual_seed(1)
     image = torch.randn(b, 3, 256, 256, generator=g).to(torch.bfloat16).to(dev)
+    med = lambda fn: statistics.median(timed(fn, dev) for _ in range(10))
     print(f"# default CLIP bf16, b = {b}, n = {n}; {args.rounds} alternating rounds after {args.warmup} warm-up rounds; times in ms (median)")
-    print("# fill_target fill R max_len | step_off step_on on/off | reserved_off_GiB reserved_on_GiB | varlen_attn_fwd varlen_attn_bwd (one layer, 8 heads)")
+    print("# off = pack_text off (pruned dense tower); on = pack_text; pool = pack_text + pack_text_pool_last")
+    print("# fill_target fill R max_len | step_off step_on step_pool on/off pool/off pool/on | reserved_off_GiB reserved_on_GiB reserved_pool_GiB | "
+          "varlen_attn_fwd varlen_attn_bwd pool_varlen_fwd pool_varlen_bwd (one layer, 8 heads) | attn_pool_fwd attn_pool_bwd (dense, fill 1 only)")
     for f in (1 / 16, 1 / 4, 1.0):
         text = torch.randint(1, 10000, (b, n), generator=g)
         if f < 1.0:
@@ -48,36 +55,48 @@ def main():
         lay = text_layout(text, pad_id=0)
         text = text.to(dev)
 
-        def step(pack):
-            model.pack_text = pack
+        def step(mode):
+            model.pack_text, model.pack_text_pool_last = mode != "off", mode == "pool"
             model.zero_grad(set_to_none=True)
-            model(text, image, return_loss=True, **(dict(text_layout=lay) if pack else {})).backward()
+            model(text, image, return_loss=True, **(dict(text_layout=lay) if mode != "off" else {})).backward()
 
-        times = {False: [], True: []}
+        times = {m: [] for m in MODES}
         for r in range(args.warmup + args.rounds):
-            for pack in (False, True):
-                t = timed(lambda: step(pack), dev)
+            for mode in MODES:
+                t = timed(lambda: step(mode), dev)
                 if r >= args.warmup:
-                    times[pack].append(t)
+                    times[mode].append(t)
         reserved = {}
-        for pack in (False, True):
+        for mode in MODES:
             model.zero_grad(set_to_none=True)
             torch.cuda.synchronize(dev)
             torch.cuda.empty_cache()
             torch.cuda.reset_peak_memory_stats(dev)
-            step(pack)
+            step(mode)
             torch.cuda.synchronize(dev)
-            reserved[pack] = torch.cuda.max_memory_reserved(dev) / 2 ** 30
+            reserved[mode] = torch.cuda.max_memory_reserved(dev) / 2 ** 30
+        model.zero_grad(set_to_none=True)
         layd = lay.to(dev)
         qkv = torch.randn(lay.R, 3 * 8 * 64, device=dev).to(torch.bfloat16)
         do = torch.randn(lay.R, 8 * 64, device=dev).to(torch.bfloat16)
         out, lse = ops.attention_varlen_fwd(qkv, layd.cu, lay.max_len, 8, 0.125)
-        tf = statistics.median(timed(lambda: ops.attention_varlen_fwd(qkv, layd.cu, lay.max_len, 8, 0.125), dev) for _ in range(10))
-        tb = statistics.median(timed(lambda: ops.attention_varlen_bwd(qkv, layd.cu, lay.max_len, out, do, lse, 8, 0.125), dev) for _ in range(10))
-        off, on = statistics.median(times[False]), statistics.median(times[True])
-        print(f"{f:.4f} {lay.R / (b * (n + 1)):.4f} {lay.R} {lay.max_len} | {off:.2f} {on:.2f} {on / off:.3f} | {reserved[False]:.2f} {reserved[True]:.2f} | "
-              f"{tf:.3f} {tb:.3f}", flush=True)
-        del qkv, do, out, lse
+        tf = med(lambda: ops.attention_varlen_fwd(qkv, layd.cu, lay.max_len, 8, 0.125))
+        tb = med(lambda: ops.attention_varlen_bwd(qkv, layd.cu, lay.max_len, out, do, lse, 8, 0.125))
+        del out, lse
+        q, kv, doc = qkv[:b, :512].contiguous(), qkv[:, 512:].contiguous(), do[:b].contiguous()
+        oc, lsec = ops.attention_pool_varlen_fwd(q, kv, layd.cu, 8, 0.125)
+        pf = med(lambda: ops.attention_pool_varlen_fwd(q, kv, layd.cu, 8, 0.125))
+        pb = med(lambda: ops.attention_pool_varlen_bwd(q, kv, layd.cu, oc, doc, lsec, 8, 0.125))
+        dense = "- -"
+        if lay.R == b * (n + 1):
+            kvd = kv.view(b, n + 1, 1024)
+            df = med(lambda: ops.attention_pool_fwd(q, kvd, None, 8, 0.125))
+            db = med(lambda: ops.attention_pool_bwd(q, kvd, None, oc, doc, lsec, 8, 0.125))
+            dense = f"{df:.3f} {db:.3f}"
+        off, on, pool = (statistics.median(times[m]) for m in MODES)
+        print(f"{f:.4f} {lay.R / (b * (n + 1)):.4f} {lay.R} {lay.max_len} | {off:.2f} {on:.2f} {pool:.2f} {on / off:.3f} {pool / off:.3f} {pool / on:.3f} | "
+              f"{reserved['off']:.2f} {reserved['on']:.2f} {reserved['pool']:.2f} | {tf:.3f} {tb:.3f} {pf:.3f} {pb:.3f} | {dense}", flush=True)
+        del qkv, do, q, kv, doc, oc, lsec
 
 
 if __name__ == "__main__":

@@ -64,6 +64,8 @@ _SIGNATURES = {
     "xclip_attention_pool_bwd": (c_int, [P, P, P, P, P, P, P, P, L, L, L, L, F, L, I, P]),
     "xclip_attention_varlen_fwd": (c_int, [P, P, P, P, L, L, L, L, L, F, I, P]),
     "xclip_attention_varlen_bwd": (c_int, [P, P, P, P, P, P, L, L, L, L, L, F, I, P]),
+    "xclip_attention_pool_varlen_fwd": (c_int, [P, P, P, P, P, L, L, L, L, F, I, P]),
+    "xclip_attention_pool_varlen_bwd": (c_int, [P, P, P, P, P, P, P, P, L, L, L, L, F, I, P]),
     "xclip_dropout": (c_int, [P, P, L, F, U, I, P]),
     "xclip_filip_reduce": (c_int, [P, L, P, P, P, P, L, P, P, P, L, L, L, L, L, L, I, P]),
     "xclip_filip_fused_ok": (c_int, [L, L, L, I]),
@@ -78,6 +80,7 @@ _SIGNATURES = {
     "xclip_layernorm_chain_bwd_workspace_bytes": (c_int64, [L, L]),
     "xclip_layernorm_chain_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, L, L, L, I, P]),
     "xclip_gather_rows": (c_int, [P, L, P, P, L, L, I, P]),
+    "xclip_rows_add_at": (c_int, [P, L, P, P, L, L, I, P]),
     "xclip_cross_entropy_fwd": (c_int, [P, L, P, L, L, P, P, I, P]),
     "xclip_cross_entropy_bwd": (c_int, [P, L, P, P, P, L, L, I, P]),
     "xclip_batchnorm_workspace_bytes": (c_int64, [L, L]),
@@ -112,7 +115,7 @@ _SIGNATURES = {
     "xclip_grad_accumulate": (c_int, [P, L, L, I, P, I, P]),
 }
 EXPORTS = tuple(_SIGNATURES)
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 
 def _bind(path: str):

@@ -211,14 +211,18 @@ class TextTransformer(nn.Module):
     def forward(self, x, mask=None, *, pool_row: Optional[int] = None, layout=None):
         """pool_row = r (not a reference keyword): the caller will read row r of every sample's encoding and nothing else -- the result is
         then [b, dim], and the last layer's row-wise part (to_out, feed-forward, norm_out) runs on those rows alone (functional.stack_forward).
-        layout (packing.TextLayout of x under its key mask; CLIP.pack_text): the tower runs on the kept rows only and returns the CLS rows [b, dim]"""
+        layout (packing.TextLayout of x under its key mask; CLIP.pack_text): the tower runs on the kept rows only and returns the CLS rows [b, dim];
+        with pool_row = 0 its last layer is the pooled one as well (CLIP.pack_text_pool_last)"""
         t = self.transformer
         pos = self.abs_pos_emb.weight if exists(self.abs_pos_emb) else None
         if layout is not None:
             if layout.batch != x.shape[0] or layout.n != x.shape[1]:
                 raise ValueError(f"text_layout was built for a [{layout.batch}, {layout.n}] token batch, the text is {tuple(x.shape)}")
+            if pool_row not in (None, 0):
+                raise ValueError("a packed text tower returns the CLS rows: pool_row is 0 (the pooled last layer) or None (the dense one)")
             return XF.text_encode_packed(layout, self.token_emb.weight, pos, self.cls_token, t.stack_params(),
-                                         t.spec(rotary=self.rotary_pos_emb.frequencies(x.device) if exists(self.rotary_pos_emb) else None))
+                                         t.spec(rotary=self.rotary_pos_emb.frequencies(x.device) if exists(self.rotary_pos_emb) else None),
+                                         pool_last=pool_row == 0)
         return XF.text_encode(x, mask, self.token_emb.weight, pos, self.cls_token, t.stack_params(),
                               t.spec(rotary=self.rotary_pos_emb.frequencies(x.device) if exists(self.rotary_pos_emb) else None), pool_row=pool_row)
 
@@ -447,6 +451,10 @@ class CLIP(nn.Module):
         # opt-in: the text tower runs on the rows its key mask keeps and nothing else (x_clip_amd.packing; README "Packed text tower").  Same
         # tokens, same loss and gradients; padded rows are never computed.  Off: every launch as before.  Raises for what reads every row
         self._pack_text = False
+        # opt-in, only read where pack_text is on: the packed tower's LAST layer runs its attention as one query per (sample, head) and
+        # everything behind it on the CLS rows alone -- what prune_unused_rows does for the dense tower (functional._layer_forward_pooled_packed).
+        # Same function; the pooled layer rounds at other points than the dense one, so bf16 results move by ulps.  Off: pack_text as before
+        self.pack_text_pool_last = False
         # >1: the text batch runs through the text tower in that many slices, each on its own HIP stream.  The tower alternates
         # MFMA-bound GEMMs with HBM-bound row kernels; with two slices in flight one slice's LayerNorm / GEGLU kernels (no LDS, few
         # registers: they fit on a CU beside a persistent GEMM work-group) run under the other slice's GEMMs.  Encoders are row
@@ -535,7 +543,10 @@ class CLIP(nn.Module):
             if not cls_row_only:
                 raise NotImplementedError("CLIP.pack_text is not available with return_encodings=True (the encoding of every row is returned)")
             from .packing import text_layout
-            return text_args, dict(layout=layout if layout is not None else text_layout(text, self.text_pad_id, mask=text_mask))
+            text_kwargs = dict(layout=layout if layout is not None else text_layout(text, self.text_pad_id, mask=text_mask))
+            if self.pack_text_pool_last:
+                text_kwargs["pool_row"] = 0
+            return text_args, text_kwargs
         if layout is not None:
             raise ValueError("text_layout was passed but CLIP.pack_text is off")
         if (cls_row_only and self.prune_unused_rows and isinstance(self.text_transformer, TextTransformer) and self.text_has_cls_token

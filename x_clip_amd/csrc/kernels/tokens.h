@@ -618,6 +618,26 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const T* __restrict__ 
         st16(out + r * (long)D + c * VEC, ld16(src + (long)idx[r] * lds_ + c * VEC));
     }
 }
+// the gather's transpose onto rows that already hold a value: dst[idx[r], :] += src[r, :], summed in fp32 and rounded once.  idx strictly
+// ascending -> the rows are distinct: every element has one writer, no atomics (the packed tower's CLS rows: dq W_q and the skip gradient)
+template <typename T>
+__global__ __launch_bounds__(256) void rows_add_at_kernel(T* __restrict__ dst, long ldd, const int* __restrict__ idx,
+                                                          const T* __restrict__ src, long rows, int D) {
+    constexpr int VEC = Elem<T>::VEC;
+    const int nch = D / VEC;
+    const long total = rows * nch;
+    for (long id = (long)blockIdx.x * blockDim.x + threadIdx.x; id < total; id += (long)gridDim.x * blockDim.x) {
+        const long r = id / nch;
+        const int c = (int)(id % nch);
+        T* d = dst + (long)idx[r] * ldd + c * VEC;
+        float a[VEC], b[VEC];
+        load_vec<T>(d, a);
+        load_vec<T>(src + r * (long)D + c * VEC, b);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) a[e] += b[e];
+        store_vec<T>(d, a);
+    }
+}
 // cross-entropy over the first `cols` columns of logits [rows, ld] (any padding columns up to ld are ignored) with one int64 label
 // per row: lse[r] = log sum_c exp(x[r, c]);  *loss_accum += sum_r (lse[r] - x[r, label[r]]).  One wave per row, a wave walks rows
 // blockIdx.x * 4 + wave, + 4 gridDim.x, ...; the grid is capped (ROWLOSS_MAX_BLOCKS) and every work-group adds ONE partial sum: tens of

@@ -946,6 +946,19 @@ int xclip_gather_rows(const void* src, int64_t lds, const int32_t* idx, void* ou
     });
     return check_launch(__func__);
 }
+int xclip_rows_add_at(void* dst, int64_t ldd, const int32_t* idx, const void* src, int64_t rows, int64_t dim, int dtype, void* stream) {
+    XC_REQUIRE(dtype_ok(dtype), "bad dtype");
+    XC_REQUIRE(rows >= 0 && dim > 0 && dim % vec_of(dtype) == 0 && ldd % vec_of(dtype) == 0, "dim / row stride must be whole 16-byte chunks");
+    if (rows == 0) return 0;                                  // (an empty tensor has a null data pointer)
+    XC_REQUIRE(dst && idx && src && aligned16(dst) && aligned16(src), "null or misaligned pointer");
+    int64_t blocks = (rows * (dim / vec_of(dtype)) + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    dim3 grid((unsigned)blocks), block(256);
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((rows_add_at_kernel<T>), grid, block, 0, (hipStream_t)stream, (T*)dst, (long)ldd, idx, (const T*)src, (long)rows, (int)dim);
+    });
+    return check_launch(__func__);
+}
 int xclip_cross_entropy_fwd(const void* logits, int64_t ld, const int64_t* labels, int64_t rows, int64_t cols, float* lse, float* loss_accum,
                             int dtype, void* stream) {
     XC_REQUIRE(dtype_ok(dtype), "bad dtype");

@@ -13,6 +13,7 @@
 #include "kernels/attention6.h"
 #include "kernels/attention7.h"
 #include "kernels/attention_pool.h"
+#include "kernels/attention_pool_varlen.h"
 #include "kernels/attention_varlen.h"
 
 using namespace xc;
@@ -371,6 +372,63 @@ int xclip_attention_varlen_bwd(const void* qkv, const int32_t* cu, const void* o
     } else {
         by_dtype(dtype, [&](auto t) { launch_attn_varlen_plain<typename decltype(t)::type>(p, head_dim, true, st); });
     }
+    return check_launch(__func__);
+}
+
+}  // extern "C"
+
+// ---- one query row per (sample, head) over samples of different lengths (kernels/attention_pool_varlen.h) ----
+static int attn_pool_varlen_setup(const char* fn, int64_t rows, int64_t batch, int64_t heads, int64_t head_dim, float scale, int dtype, bool ptrs_ok) {
+#define XC_REQ(cond, msg) do { if (!(cond)) return xcapi::fail(fn, msg); } while (0)
+    XC_REQ(xcapi::dtype_ok(dtype), "bad dtype");
+    XC_REQ(batch >= 0 && heads > 0 && rows >= 0, "bad shape");
+    XC_REQ(rows < ((int64_t)1 << 31) && batch * heads < ((int64_t)1 << 31), "too many rows");
+    XC_REQ(head_dim == 64 || head_dim == 128, "head_dim must be 64 or 128 (narrower / in-between widths are zero-padded by the caller)");
+    XC_REQ(batch == 0 || ptrs_ok, "pointers must be non-null and 16-byte aligned");
+    XC_REQ(scale > 0.f, "scale must be positive");
+    return 0;
+#undef XC_REQ
+}
+template <typename T>
+static void launch_attn_pool_varlen(const xc::AttnPoolVarlenParams& p, int64_t head_dim, bool backward, hipStream_t st) {
+    const dim3 grid((unsigned)(((int64_t)p.batch * p.heads + 3) / 4)), block(256);
+    if (head_dim == 64) {
+        if (backward) hipLaunchKernelGGL((xc::attn_pool_varlen_bwd_kernel<T, 64>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((xc::attn_pool_varlen_fwd_kernel<T, 64>), grid, block, 0, st, p);
+    } else {
+        if (backward) hipLaunchKernelGGL((xc::attn_pool_varlen_bwd_kernel<T, 128>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((xc::attn_pool_varlen_fwd_kernel<T, 128>), grid, block, 0, st, p);
+    }
+}
+
+extern "C" {
+
+int xclip_attention_pool_varlen_fwd(const void* q, const void* kv, const int32_t* cu, void* out, float* lse, int64_t rows, int64_t batch,
+                                    int64_t heads, int64_t head_dim, float scale, int dtype, void* stream) {
+    // (kv may be null when no sample owns a row: nothing is read through it then)
+    const int rc = attn_pool_varlen_setup(__func__, rows, batch, heads, head_dim, scale, dtype,
+                                          q && (kv || rows == 0) && cu && out && lse && aligned16(q) && aligned16(kv) && aligned16(out));
+    if (rc != 0 || batch == 0) return rc;
+    AttnPoolVarlenParams p;
+    memset(&p, 0, sizeof(p));
+    p.q = q; p.kv = kv; p.cu = cu; p.out = out; p.lse = lse;
+    p.batch = (int)batch; p.heads = (int)heads; p.rows = (int)rows; p.scale = scale;
+    by_dtype(dtype, [&](auto t) { launch_attn_pool_varlen<typename decltype(t)::type>(p, head_dim, false, (hipStream_t)stream); });
+    return check_launch(__func__);
+}
+
+int xclip_attention_pool_varlen_bwd(const void* q, const void* kv, const int32_t* cu, const void* out, const void* dout, const float* lse,
+                                    void* dq, void* dkv, int64_t rows, int64_t batch, int64_t heads, int64_t head_dim, float scale, int dtype,
+                                    void* stream) {
+    const int rc = attn_pool_varlen_setup(__func__, rows, batch, heads, head_dim, scale, dtype,
+                                          q && ((kv && dkv) || rows == 0) && cu && out && dout && lse && dq && aligned16(q) && aligned16(kv) &&
+                                              aligned16(out) && aligned16(dout) && aligned16(dq) && aligned16(dkv));
+    if (rc != 0 || batch == 0) return rc;
+    AttnPoolVarlenParams p;
+    memset(&p, 0, sizeof(p));
+    p.q = q; p.kv = kv; p.cu = cu; p.out = const_cast<void*>(out); p.lse = const_cast<float*>(lse); p.dout = dout; p.dq = dq; p.dkv = dkv;
+    p.batch = (int)batch; p.heads = (int)heads; p.rows = (int)rows; p.scale = scale;
+    by_dtype(dtype, [&](auto t) { launch_attn_pool_varlen<typename decltype(t)::type>(p, head_dim, true, (hipStream_t)stream); });
     return check_launch(__func__);
 }
 

@@ -318,6 +318,8 @@ def _add_to_pooled_rows(full: Tensor, add: Tensor, B: int, n: int, row: int) -> 
 
 
 def _layer_forward_pooled(x: Tensor, W: LayerWeights, c: _Pass, row: int):
+    if c.layout is not None:
+        return _layer_forward_pooled_packed(x, W, c)
     spec, B, n, inner = c.spec, c.B, c.n, c.spec.inner
     M, D = x.shape
     h, m1, r1 = ops.layernorm_fwd(x, W.g_attn)
@@ -342,6 +344,8 @@ def _layer_forward_pooled(x: Tensor, W: LayerWeights, c: _Pass, row: int):
 
 def _layer_backward_pooled(dx2: Tensor, t: LayerTape, W: LayerWeights, need: LayerWeights, dg: LayerWeights, c: _Pass, sg: _SideGemm, row: int):
     """dx2 [B, D]: gradient w.r.t. the pooled rows of the layer output -> (gradient w.r.t. the layer input [B n, D], weight gradients)"""
+    if c.layout is not None:
+        return _layer_backward_pooled_packed(dx2, t, W, need, dg, c, sg)
     spec, B, n, inner = c.spec, c.B, c.n, c.spec.inner
     M, D = t.x.shape
     dx1, dp, d_ff1, d_ff2 = _ffn_backward(dx2, t, W, need, dg, c, sg, 0)
@@ -375,6 +379,47 @@ def _layer_backward_pooled(dx2: Tensor, t: LayerTape, W: LayerWeights, need: Lay
     return dx, dict(w_qkv=d_qkv, w_out=d_out, w_ff1=d_ff1, w_ff2=d_ff2)
 
 
+# ---- the same for a packed batch (c.layout): the pooled row is the FIRST row of every sample, row cu[s] of the [R, D] arrays ----------------
+# The rows of a sample are not a fixed stride apart, so the strided views above become gathers (xclip_gather_rows by cu[:-1]) and the two
+# "add into the pooled rows" become xclip_rows_add_at; the one-query attention reads each sample's own keys through cu
+# (attention_pool_varlen.h).  Same algebra and the same rounding points as the dense pooled layer above.
+def _layer_forward_pooled_packed(x: Tensor, W: LayerWeights, c: _Pass):
+    spec, lay, inner = c.spec, c.layout, c.spec.inner
+    (R, D), B, first = x.shape, c.layout.batch, c.layout.cu[:-1]
+    h, m1, r1 = ops.layernorm_fwd(x, W.g_attn)                                         # PreNorm, every kept row   :126
+    xc = ops.gather_rows(x, first)                                                     # the skip connection's pooled rows
+    hc = ops.gather_rows(h, first)
+    q = ops.gemm(hc, W.w_qkv[:inner], B, inner, D)                                     # to_qkv: the query third on B rows,
+    kv = ops.gemm(h, W.w_qkv[inner:], R, 2 * inner, D)                                 # keys | values on all R      :216
+    oc, lse = ops.attention_pool_varlen_fwd(q, kv, lay.cu, spec.heads, spec.scale, spec.head_slot)
+    p = ops.gemm(oc, W.w_out, B, D, inner)                                             # from here on: B rows
+    x2, ff = _ffn_forward(p, xc, W, c, 0)
+    return x2, LayerTape(x=x, h=h, m1=m1, r1=r1, qkv=(q, kv, hc), o=oc, lse=lse, p=p, **ff)
+
+
+def _layer_backward_pooled_packed(dx2: Tensor, t: LayerTape, W: LayerWeights, need: LayerWeights, dg: LayerWeights, c: _Pass, sg: _SideGemm):
+    """dx2 [B, D]: gradient w.r.t. the CLS rows of the layer output -> (gradient w.r.t. the layer input [R, D], weight gradients)"""
+    spec, lay, inner = c.spec, c.layout, c.spec.inner
+    (R, D), B, first = t.x.shape, c.layout.batch, c.layout.cu[:-1]
+    dx1, dp, d_ff1, d_ff2 = _ffn_backward(dx2, t, W, need, dg, c, sg, 0)
+    q, kv, hc = t.qkv
+    d_out = sg.wgrad(dp, t.o, D, inner, B, W.w_out) if need.w_out else None
+    doc = ops.gemm(dp, W.w_out, B, inner, D, b_kmajor=True)
+    dq, dkv = ops.attention_pool_varlen_bwd(q, kv, lay.cu, t.o, doc, t.lse, spec.heads, spec.scale, spec.head_slot)
+    # d h = dkv W_kv on every row, + dq W_q on the CLS rows
+    dh = ops.gemm(dkv, W.w_qkv[inner:], R, D, 2 * inner, b_kmajor=True)
+    ops.rows_add_at(dh, first, ops.gemm(dq, W.w_qkv[:inner], B, D, inner, b_kmajor=True))
+    d_qkv = None
+    if need.w_qkv:                                             # both parts of the weight gradient into ONE tensor (a bucket slice, if claimed)
+        d_qkv = _grad_out(W.w_qkv, (3 * inner, D), dp.dtype, dp.device)
+        sg.wgrad_into(dq, hc, inner, D, B, d_qkv[:inner])
+        sg.wgrad_into(dkv, t.h, 2 * inner, D, R, d_qkv[inner:])
+    del dkv
+    dx, _ = ops.layernorm_bwd(dh, t.x, W.g_attn, t.m1, t.r1, dg=dg.g_attn)
+    ops.rows_add_at(dx, first, dx1)                            # the skip connection carries a gradient on the CLS rows only
+    return dx, dict(w_qkv=d_qkv, w_out=d_out, w_ff1=d_ff1, w_ff2=d_ff2)
+
+
 # ---- the whole stack: norm_in -> depth x (attention, feed-forward) -> norm_out ------------------------------------------
 def can_pool(spec: StackSpec) -> bool:
     """may the last layer run on one row per sample (`pool_row`)?  Dropout masks are indexed by the element's position in the dense
@@ -386,10 +431,11 @@ def stack_forward(x0: Tensor, B: int, n: int, spec: StackSpec, params: Sequence[
                   out: Optional[Tensor] = None, out_group: int = 0, keep_tape: bool = True, pool_row: Optional[int] = None, layout=None):
     """x0 [B*n, D] -> norm_out(...) [B*n, D] (or written into `out`, see ops.layernorm_fwd) and the backward tape.
     pool_row = r: only token row r of every sample is wanted -> [B, D] (the last layer's row-wise part runs on those rows alone).
-    layout (packing.TextLayout): x0 is [R, D], the kept rows end to end (_Pass); every layer runs on all R rows, no pooled last layer"""
+    layout (packing.TextLayout): x0 is [R, D], the kept rows end to end (_Pass); every layer runs on all R rows -- with pool_row = 0 (the first
+    row of every sample, its CLS row) the last layer's row-wise part runs on those B rows (_layer_forward_pooled_packed) -> [B, D]"""
     assert len(params) == 2 + LAYER_PARAMS * spec.depth
     assert pool_row is None or (can_pool(spec) and out is None and 0 <= pool_row < n)
-    assert layout is None or (pool_row is None and mask is None and out is None and x0.shape[0] == layout.R)
+    assert layout is None or (pool_row in (None, 0) and mask is None and out is None and x0.shape[0] == layout.R)
     x, m_in, r_in = ops.layernorm_fwd(x0, params[0])
     # dropout: one 64-bit seed per pass from torch's CPU generator (no device sync; torch.manual_seed makes it reproducible); layer l
     # uses seed + 2 l (attention) and seed + 2 l + 1 (feed-forward); the backward and a checkpointed re-run regenerate the same masks
@@ -562,29 +608,31 @@ def text_encode(tokens: Tensor, mask: Optional[Tensor], E: Tensor, P: Optional[T
 
 class _PackedTextEncodeFn(torch.autograd.Function):
     """the text encoder on the kept rows alone (packing.TextLayout) -> the CLS row of every sample [b, D].  Padded rows are never embedded,
-    normalised, multiplied or attended from, forward or backward; no [b (n + 1), D] array is allocated on this path."""
+    normalised, multiplied or attended from, forward or backward; no [b (n + 1), D] array is allocated on this path.
+    pool_last: the stack is asked for the CLS rows (stack_forward `pool_row = 0`): its last layer runs everything behind the attention on them alone"""
 
     @staticmethod
-    def forward(ctx, spec: StackSpec, layout, grad_mode: bool, E: Tensor, P: Optional[Tensor], cls: Tensor, *stack: Tensor):
+    def forward(ctx, spec: StackSpec, layout, grad_mode: bool, pool_last: bool, E: Tensor, P: Optional[Tensor], cls: Tensor, *stack: Tensor):
         keep = grad_mode and any(ctx.needs_input_grad)
         x0 = ops.text_embed_packed_fwd(layout.tok, layout.pos, E, P, cls)                # token_emb + pos, the cls rows   :320-331
-        y, tape = stack_forward(x0, layout.batch, layout.max_len, spec, stack, None, keep_tape=keep, layout=layout)
+        y, tape = stack_forward(x0, layout.batch, layout.max_len, spec, stack, None, keep_tape=keep, pool_row=0 if pool_last else None, layout=layout)
         ctx.save_for_backward(*stack)
-        ctx.spec, ctx.layout, ctx.tape = spec, layout, tape
+        ctx.spec, ctx.layout, ctx.tape, ctx.pool_last = spec, layout, tape, pool_last
         ctx.meta = (E.shape[0], E.shape[1], 0 if P is None else P.shape[0], E.dtype)
-        return ops.gather_rows(y, layout.cu[:-1])                                        # enc_text[:, 0]                  :708
+        return y if pool_last else ops.gather_rows(y, layout.cu[:-1])                    # enc_text[:, 0]                  :708
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
         vocab, D, npos, dtype = ctx.meta
         lay = ctx.layout
-        need = ctx.needs_input_grad[3:]
-        dy = _contig_grad(dy, (lay.batch, D), dtype, lay.cu.device)
-        # dy into the CLS rows of a zeroed [R, D]: as a gather, row r takes dy[s] where r = cu[s] and the appended zero row elsewhere
-        src = torch.full((lay.R,), lay.batch, dtype=torch.int32, device=dy.device)
-        src[lay.cu[:-1].long()] = torch.arange(lay.batch, dtype=torch.int32, device=dy.device)
-        dyr = ops.gather_rows(torch.cat([dy, dy.new_zeros(1, D)], dim=0), src)
+        need = ctx.needs_input_grad[4:]
+        dyr = _contig_grad(dy, (lay.batch, D), dtype, lay.cu.device)
+        if not ctx.pool_last:
+            # dy into the CLS rows of a zeroed [R, D]: as a gather, row r takes dy[s] where r = cu[s] and the appended zero row elsewhere
+            src = torch.full((lay.R,), lay.batch, dtype=torch.int32, device=dyr.device)
+            src[lay.cu[:-1].long()] = torch.arange(lay.batch, dtype=torch.int32, device=dyr.device)
+            dyr = ops.gather_rows(torch.cat([dyr, dyr.new_zeros(1, D)], dim=0), src)
         dx0, sgrads = stack_backward(dyr, _take_tape(ctx), lay.batch, lay.max_len, ctx.spec, ctx.saved_tensors, None, need[3:], layout=lay)
         dE = dP = dcls = None
         if need[0] or need[1] or need[2]:
@@ -593,13 +641,15 @@ class _PackedTextEncodeFn(torch.autograd.Function):
             dE = ops.cast_from_f32(aE, dtype) if need[0] else None
             dP = ops.cast_from_f32(aP, dtype) if (need[1] and aP is not None) else None
             dcls = ops.cast_from_f32(acls, dtype) if need[2] else None
-        return (None, None, None, dE, dP, dcls, *sgrads)
+        return (None, None, None, None, dE, dP, dcls, *sgrads)
 
 
-def text_encode_packed(layout, E: Tensor, P: Optional[Tensor], cls: Optional[Tensor], stack: Sequence[Tensor], spec: StackSpec) -> Tensor:
+def text_encode_packed(layout, E: Tensor, P: Optional[Tensor], cls: Optional[Tensor], stack: Sequence[Tensor], spec: StackSpec,
+                       pool_last: bool = False) -> Tensor:
     """TextTransformer.forward (x_clip.py:317-338) followed by `[:, 0]` (x_clip.py:708) for a packed batch -> [b, D]: the same function of
-    the same tokens as text_encode(..., mask, pool_row=0), computed on the kept rows only.  Every layer runs on all R rows (there is no
-    varlen one-query attention: the dense path's pooled last layer has no packed twin)."""
+    the same tokens as text_encode(..., mask, pool_row=0), computed on the kept rows only.  Every layer runs on all R rows; with pool_last the
+    last one runs its attention as one query per (sample, head) and everything behind it on the b CLS rows (the packed twin of the dense
+    path's pooled last layer, with its rounding points: see _layer_forward_pooled)."""
     if cls is None:
         raise NotImplementedError("pack_text: the packed text tower returns the CLS row (text_has_cls_token=True)")
     if spec.rotary is not None or spec.causal or spec.attn_dropout > 0.0 or spec.ff_dropout > 0.0:
@@ -610,7 +660,7 @@ def text_encode_packed(layout, E: Tensor, P: Optional[Tensor], cls: Optional[Ten
         raise IndexError(f"text length {layout.n} exceeds max_seq_len {P.shape[0]}")
     if layout.cu.device != E.device:
         layout = layout.to(E.device)
-    return _PackedTextEncodeFn.apply(spec, layout, torch.is_grad_enabled(), E, P, cls, *stack)
+    return _PackedTextEncodeFn.apply(spec, layout, torch.is_grad_enabled(), bool(pool_last) and can_pool(spec), E, P, cls, *stack)
 
 
 # ---- vision encoder -----------------------------------------------------------------------------------------------------------

@@ -818,6 +818,46 @@ def attention_pool_bwd(q: Tensor, kv: Tensor, mask: Optional[Tensor], out: Tenso
     return dq, dkv
 
 
+def attention_pool_varlen_fwd(q: Tensor, kv: Tensor, cu: Tensor, heads: int, scale: float, head_dim: int = 64) -> Tuple[Tensor, Tensor]:
+    """ONE query row per (sample, head) over samples of different lengths laid end to end: q [b, heads*head_dim], kv [R, 2*heads*head_dim]
+    (keys | values of every kept row), cu int32 [b + 1] (sample s = rows cu[s] .. cu[s+1]) -> out [b, heads*head_dim], lse fp32 [b, heads]"""
+    _dev_check(q, kv, cu)
+    q, kv = _c(q), _c(kv)
+    R, w = kv.shape
+    b = cu.numel() - 1
+    assert head_dim in (64, 128) and w == 2 * heads * head_dim and tuple(q.shape) == (b, heads * head_dim) and q.dtype == kv.dtype
+    assert cu.dtype == torch.int32 and cu.dim() == 1 and cu.is_contiguous()
+    out = torch.empty_like(q)
+    lse = torch.empty(b, heads, dtype=torch.float32, device=q.device)
+    probe = _probe(q)
+    ev0 = probe.begin(q) if probe is not None else None
+    _lib.check(_lib.lib().xclip_attention_pool_varlen_fwd(q.data_ptr(), kv.data_ptr(), cu.data_ptr(), out.data_ptr(), lse.data_ptr(), R, b, heads,
+                                                          head_dim, scale, dtype_code(q), _stream(q)), "xclip_attention_pool_varlen_fwd")
+    if probe is not None:      # (bytes only, as the varlen kernels: k, v in (+ q), o out)
+        probe.end(q, ev0, "attention", 0.0, (2 * R + 2 * b) * heads * head_dim * q.element_size(), "attn_pool_varlen_fwd")
+    return out, lse
+
+
+def attention_pool_varlen_bwd(q: Tensor, kv: Tensor, cu: Tensor, out: Tensor, dout: Tensor, lse: Tensor, heads: int, scale: float,
+                              head_dim: int = 64) -> Tuple[Tensor, Tensor]:
+    """-> dq [b, heads*head_dim], dkv [R, 2*heads*head_dim] (every row a sample owns written)"""
+    _dev_check(q, kv, cu, out, dout, lse)
+    q, kv, out, dout = _c(q), _c(kv), _c(out), _c(dout)
+    R, b = kv.shape[0], cu.numel() - 1
+    assert lse.dtype == torch.float32 and lse.is_contiguous() and tuple(lse.shape) == (b, heads) and out.shape == q.shape
+    assert dout.shape == q.shape and dout.dtype == q.dtype and cu.dtype == torch.int32 and cu.is_contiguous()
+    dq = torch.empty_like(q)
+    dkv = torch.empty_like(kv)
+    probe = _probe(q)
+    ev0 = probe.begin(q) if probe is not None else None
+    _lib.check(_lib.lib().xclip_attention_pool_varlen_bwd(q.data_ptr(), kv.data_ptr(), cu.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(),
+                                                          dq.data_ptr(), dkv.data_ptr(), R, b, heads, head_dim, scale, dtype_code(q), _stream(q)),
+               "xclip_attention_pool_varlen_bwd")
+    if probe is not None:      # k, v in, dk, dv out
+        probe.end(q, ev0, "attention", 0.0, (4 * R + 4 * b) * heads * head_dim * q.element_size(), "attn_pool_varlen_bwd")
+    return dq, dkv
+
+
 def dropout(x: Tensor, p: float, seed: int, out: Optional[Tensor] = None) -> Tensor:
     """y = x * keep / (1 - p) with the keep-mask of (seed, flat element index) (csrc/kernels/common.h drop_hash; reference nn.Dropout in
     FeedForward, x_clip.py:193-194).  The same call on the gradient is the backward.  out=x works in place."""
@@ -1286,6 +1326,18 @@ def gather_rows(src: Tensor, idx: Tensor) -> Tensor:
     _lib.check(_lib.lib().xclip_gather_rows(src.data_ptr(), src.stride(0), idx.data_ptr(), out.data_ptr(), idx.numel(), src.shape[1],
                                             dtype_code(src), _stream(src)), "xclip_gather_rows")
     return out
+
+
+def rows_add_at(dst: Tensor, idx: Tensor, src: Tensor) -> Tensor:
+    """dst[idx[r]] += src[r], in place (fp32 sum, rounded once): dst [rows_out, D] (row stride free), src [rows, D], idx int32 [rows] STRICTLY
+    ascending -- distinct rows, so no two writers meet"""
+    _dev_check(dst, idx, src)
+    src = _c(src)
+    assert dst.dim() == 2 and dst.stride(1) == 1 and src.dim() == 2 and src.shape[1] == dst.shape[1] and src.dtype == dst.dtype
+    assert idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() == src.shape[0]
+    _lib.check(_lib.lib().xclip_rows_add_at(dst.data_ptr(), dst.stride(0), idx.data_ptr(), src.data_ptr(), idx.numel(), dst.shape[1],
+                                            dtype_code(dst), _stream(dst)), "xclip_rows_add_at")
+    return dst
 
 
 def cross_entropy_fwd(logits: Tensor, cols: int, labels: Tensor, loss_accum: Tensor) -> Tensor:
