@@ -126,6 +126,22 @@ def case_varlen_equals_dense(dev, dtype, B, n, heads, slot):
     K.close(dqkv, d_dqkv.view(B * n, -1).double(), dtype, "varlen attn dqkv " + tag, mult=3.0, ulps=2.0, unit="scale")
 
 
+EQUAL_BITS_NS = (33, 65, 66, 97)          # one wave with an ordinary tail, a single tail, a two-row tail, three waves past a dip
+
+
+def case_varlen_equals_dense_bits(dev, n, B=2, heads=3, slot=64):
+    """bf16, B samples of one length, max_len = n, no mask: the head-resident packed kernels ARE the dense ones (one body in attention3.h, the
+    unit's rows found from cu instead of (sample, n)) -- out, lse and dqkv bit for bit"""
+    qkv, dout = varlen_data((n,) * B, heads, slot, slot, BF16, dev, seed=3)
+    scale = slot ** -0.5
+    out, lse, dqkv = varlen_launch(qkv, dout, _cu((n,) * B, dev), n, heads, slot, scale)
+    d_out, d_lse = ops.attention_fwd(qkv.view(B, n, -1), None, heads, scale, False, slot)
+    d_dqkv = ops.attention_bwd(qkv.view(B, n, -1), None, d_out, dout.view(B, n, -1), d_lse, heads, scale, False, slot)
+    for name, a, b in (("out", out, d_out.view(B * n, -1)), ("lse", lse, d_lse.permute(1, 0, 2).reshape(heads, B * n)),
+                       ("dqkv", dqkv, d_dqkv.view(B * n, -1))):
+        assert torch.equal(_bits(a), _bits(b.contiguous())), f"{name}: packed and dense differ in bits at n {n}"
+
+
 def case_varlen_full(dev, dtype=BF16, samples=256, heads=8, slot=64, repeats=3):
     """GPU: >= 1024 (sample, head) units, every head checked against the fp64 reference evaluated on the device, three launches bit-identical"""
     lens = tuple(LENS_A[i % len(LENS_A)] for i in range(samples))

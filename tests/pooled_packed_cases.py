@@ -129,6 +129,22 @@ def case_pool_varlen_equals_dense_pool(dev, dtype, B, n, heads, slot):
     check_pool_varlen((out, lse, dq, dkv), (d_out.double(), d_lse.double(), d_dq.double(), d_dkv.view(B * n, -1).double()), dtype, tag)
 
 
+EQUAL_BITS_NS = (1, 7, 9, 70)              # one key; a partial and a whole wave-wide load of bf16 slot 64 plus one key; many loads
+
+
+def case_pool_varlen_equals_dense_pool_bits(dev, dtype, n, slot, B=3, heads=3):
+    """B samples of one length, no mask, visible_keys = n: the packed and the dense pooled kernels walk the same keys in the same order --
+    out, lse, dq and dkv bit for bit"""
+    lens = (n,) * B
+    qkv, q, kv, dout = pool_varlen_data(lens, heads, slot, slot, dtype, dev, seed=3)
+    scale = slot ** -0.5
+    got = pool_varlen_launch(q, kv, dout, P._cu(lens, dev), heads, slot, scale)
+    d_out, d_lse = ops.attention_pool_fwd(q, kv.view(B, n, -1), None, heads, scale, slot)
+    d_dq, d_dkv = ops.attention_pool_bwd(q, kv.view(B, n, -1), None, d_out, dout, d_lse, heads, scale, slot)
+    for name, a, b in zip(("out", "lse", "dq", "dkv"), got, (d_out, d_lse, d_dq, d_dkv.view(B * n, -1))):
+        assert torch.equal(P._bits(a), P._bits(b)), f"{name}: packed and dense pooled differ in bits at n {n} slot {slot}"
+
+
 def case_pool_varlen_full(dev, dtype=BF16, samples=256, heads=8, slot=64, repeats=3):
     """GPU: 2048 (sample, head) units, every unit checked against the fp64 reference evaluated on the device, three launches bit-identical"""
     lens = tuple(P.LENS_A[i % len(P.LENS_A)] for i in range(samples))

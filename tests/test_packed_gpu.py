@@ -36,6 +36,11 @@ def test_varlen_equals_dense_for_equal_lengths(n, slot, dtype):
     P.case_varlen_equals_dense(DEV, dtype, 3, n, 2, slot)
 
 
+@pytest.mark.parametrize("n", P.EQUAL_BITS_NS)
+def test_varlen_equals_dense_bit_for_bit(n):
+    P.case_varlen_equals_dense_bits(DEV, n)
+
+
 def test_varlen_attention_every_cu_busy():
     P.case_varlen_full(DEV)
 

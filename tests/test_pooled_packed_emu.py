@@ -51,6 +51,13 @@ def test_pool_varlen_equals_dense_pool_for_equal_lengths(n, slot, dtype):
 
 
 @DTYPES
+@pytest.mark.parametrize("slot", [64, 128])
+@pytest.mark.parametrize("n", Q.EQUAL_BITS_NS)
+def test_pool_varlen_equals_dense_pool_bit_for_bit(n, slot, dtype):
+    Q.case_pool_varlen_equals_dense_pool_bits(DEV, dtype, n, slot)
+
+
+@DTYPES
 @pytest.mark.parametrize("strided", [False, True], ids=["contiguous", "strided"])
 def test_rows_add_at(strided, dtype):
     Q.case_rows_add_at(DEV, dtype, strided)

@@ -45,6 +45,13 @@ def test_pool_varlen_equals_dense_pool_for_equal_lengths(n, slot, dtype):
     Q.case_pool_varlen_equals_dense_pool(DEV, dtype, 3, n, 2, slot)
 
 
+@DTYPES
+@pytest.mark.parametrize("slot", [64, 128])
+@pytest.mark.parametrize("n", Q.EQUAL_BITS_NS)
+def test_pool_varlen_equals_dense_pool_bit_for_bit(n, slot, dtype):
+    Q.case_pool_varlen_equals_dense_pool_bits(DEV, dtype, n, slot)
+
+
 def test_pool_varlen_attention_every_cu_busy():
     Q.case_pool_varlen_full(DEV)
 

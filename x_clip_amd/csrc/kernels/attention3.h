@@ -11,6 +11,8 @@
 //     wave's queries, phase B accumulates dK / dV for the wave's keys (scores are recomputed per phase, nothing is
 //     exchanged between waves, no atomics, deterministic).  Q, K, V, dO and O are read once, dQ / dK / dV written once:
 //     264 KB of traffic per head instead of the 363 KB (+ the delta pass) of the dq / dkv kernel pair.
+// Both directions are written ONCE, as device functions over one (sample, head) unit (A3Unit; a3_fwd_unit, a3_bwd_unit).  The kernels of this
+// file are the dense wrappers (unit = rows [b n, b n + n)); attention_varlen.h holds the packed ones (unit = rows [cu[b], cu[b + 1])).
 // Numerics are those of attention.h / attention2.h (fp32 online softmax, probabilities rounded to bf16 for the second
 // MFMA, masked keys get probability exactly 0).
 #pragma once
@@ -193,28 +195,49 @@ XC_DEV void a3_key_validity(unsigned char* Ms, const unsigned char* mask, long r
         Ms[k] = (k < n) && (mask == nullptr || mask[row0 + k] != 0);
 }
 
+// ---- one (sample, head) unit -----------------------------------------------------------------------------------------------
+// What the two bodies below need to know about the unit they work on, and nothing about how it was found: the dense kernels of this
+// file resolve it from (sample, n), the packed ones of attention_varlen.h from cu[sample], cu[sample + 1].  Row r of the unit is at
+// X + r * ld; every pointer already carries the head's column offset.
+struct A3Unit {
+    const bf16_t *Q, *K, *V;                                   // [n] rows, stride ldq
+    const bf16_t *O, *dO;                                      // [n] rows, stride ldo (backward inputs; the forward leaves them null)
+    bf16_t* out;                                               // forward result, stride ldo
+    bf16_t *dQ, *dK, *dV;                                      // backward results, stride ldq
+    float* lse;                                                // [n] contiguous (forward: written, backward: read)
+    long ldq, ldo;
+    int n;
+    const unsigned char* mask; long mask_row0;                 // key validity bytes mask[mask_row0 + k], or null: every key valid
+    int abl;                                                   // measurement mask (XCLIP_ATTN_ABL: 1 = skip phase A, 2 = skip phase B, 4 = the tail row
+};                                                             //  as a 33rd block, 8 = late query load); the packed kernels pass the literal 0
+XC_DEV A3Unit a3_unit(const bf16_t* qkv, const bf16_t* o, const bf16_t* dout, bf16_t* out, bf16_t* dqkv, float* lse, long row0, int n, int heads,
+                      int hh) {
+    A3Unit u;
+    u.ldq = 3L * heads * ATT_DH; u.ldo = (long)heads * ATT_DH; u.n = n;
+    u.Q = qkv + row0 * u.ldq + hh * ATT_DH; u.K = u.Q + u.ldo; u.V = u.K + u.ldo;
+    u.O = o + row0 * u.ldo + hh * ATT_DH; u.dO = dout + row0 * u.ldo + hh * ATT_DH; u.out = out + row0 * u.ldo + hh * ATT_DH;
+    u.dQ = dqkv + row0 * u.ldq + hh * ATT_DH; u.dK = u.dQ + u.ldo; u.dV = u.dK + u.ldo;
+    u.lse = lse; u.mask = nullptr; u.mask_row0 = 0; u.abl = 0;
+    return u;
+}
+
 // ---- forward ----------------------------------------------------------------------------------------------------------
-// (at most 128 VGPRs: two 8-wave work-groups of ~78 KB LDS share a CU)
-template <bool CAUSAL>
-__global__ __launch_bounds__(576) XC_FOUR_WAVES_PER_SIMD void attn3_fwd_kernel(AttnParams p) {
+// RAGGED: the launch (waves, LDS) may be sized for a longer unit than this one (attention_varlen.h) -- wave w >= a3_waves(n) then owns no
+// query block; it still loads, takes its share of a cooperative tail and meets every barrier.  Nothing else differs, and with
+// RAGGED = false `own` is the constant true.
+template <bool CAUSAL, bool RAGGED>
+XC_DEV void a3_fwd_unit(const A3Unit& u, float scale) {
     XC_LDS_DYNAMIC(lds);
-    const int n = p.n, npad = (n + 31) & ~31;
+    const int n = u.n, npad = (n + 31) & ~31;
     unsigned char* Ks = lds;
     unsigned char* Vs = Ks + npad * 128;
     unsigned char* Ms = Vs + npad * 128;                       // [npad] key validity
     float* Ts = reinterpret_cast<float*>(Ms + npad);           // [nwaves][A3_TAIL_MAX][A3_TAIL_REC] tail partials
     const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, c31 = lane & 31;
     const int wave = uniform(tid >> 6), nwaves = blockDim.x >> 6;
-    a3_stagger(p.stagger_10ns, p.first_round);
-    const int bh = xcd_remap(blockIdx.x, p.batch * p.heads);
-    const int hh = bh % p.heads, bi = bh / p.heads;
-    const long ldq = 3L * p.heads * ATT_DH;
-    const bf16_t* Qb = reinterpret_cast<const bf16_t*>(p.qkv) + (long)bi * n * ldq + hh * ATT_DH;
-    const bf16_t* Kb = Qb + (long)p.heads * ATT_DH;
-    const bf16_t* Vb = Kb + (long)p.heads * ATT_DH;
-    bf16_t* out = reinterpret_cast<bf16_t*>(p.out) + (long)bi * n * p.heads * ATT_DH + hh * ATT_DH;
-    float* lse_out = p.lse + ((long)bi * p.heads + hh) * n;
+    const long ldq = u.ldq;
     const bool coop = a3_coop_tail(n);
+    const bool own = !RAGGED || wave < a3_waves(n);            // (uniform) this wave has a 32-query block of its own
     const int tail0 = (n >> 5) << 5, ntail = n & 31;
     const int q0 = wave * 32;
     const int qrow = q0 + c31;
@@ -225,26 +248,28 @@ __global__ __launch_bounds__(576) XC_FOUR_WAVES_PER_SIMD void attn3_fwd_kernel(A
     u32x4 qf[4];
     const int qfirst = coop ? (tail0 + c31 < n ? tail0 + c31 : n - 1) : qld;
 #ifdef XCLIP_MEASURE
-    const bool q_late = (p.chunks & 8) != 0;                   // (measurement build, XCLIP_ATTN_ABL=8: the round-5 order, for the A/B)
+    const bool q_late = (u.abl & 8) != 0;                      // (measurement build, XCLIP_ATTN_ABL=8: the round-5 order, for the A/B)
 #else
     constexpr bool q_late = false;
 #endif
     if (!q_late) {
 #pragma unroll
-        for (int kb = 0; kb < 4; ++kb) qf[kb] = ld16(Qb + (long)qfirst * ldq + kb * 16 + h * 8);
+        for (int kb = 0; kb < 4; ++kb) qf[kb] = ld16(u.Q + (long)qfirst * ldq + kb * 16 + h * 8);
     }
-    a3_dma_image(Ks, Kb, ldq, n, npad, wave, nwaves, lane);
-    a3_dma_image(Vs, Vb, ldq, n, npad, wave, nwaves, lane);
-    a3_key_validity(Ms, p.mask, (long)bi * n, n, npad);
+    a3_dma_image(Ks, u.K, ldq, n, npad, wave, nwaves, lane);
+    a3_dma_image(Vs, u.V, ldq, n, npad, wave, nwaves, lane);
+    a3_key_validity(Ms, u.mask, u.mask_row0, n, npad);
     f32x16 o[2];
     wait_vmem();
     sync();
     if (q_late) {
 #pragma unroll
-        for (int kb = 0; kb < 4; ++kb) qf[kb] = ld16(Qb + (long)qfirst * ldq + kb * 16 + h * 8);
+        for (int kb = 0; kb < 4; ++kb) qf[kb] = ld16(u.Q + (long)qfirst * ldq + kb * 16 + h * 8);
     }
     const int nsub = npad >> 5;
-    const float scale2 = p.scale * 1.4426950408889634f;
+    const float scale2 = scale * 1.4426950408889634f;
+    // The tail key's validity is tested wherever it seeds an accumulator: under a key mask it may be hidden, and without one
+    // Ms[tail0] = (tail0 < n) = 1 under a single tail, so the test costs the packed kernels one LDS byte and decides nothing.
     if (coop) {                                                // tail queries x this wave's share of the key sub-tiles
 #pragma unroll
         for (int db = 0; db < 2; ++db)
@@ -252,7 +277,7 @@ __global__ __launch_bounds__(576) XC_FOUR_WAVES_PER_SIMD void attn3_fwd_kernel(A
             for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
         float m = ATT_NEG, l = 0.f;
         int tcoop = nsub;
-        if (a3_single_tail(n, p.chunks)) {                     // (uniform) the tail query against the tail key: no sub-tile of its own --
+        if (a3_single_tail(n, u.abl)) {                        // (uniform) the tail query against the tail key: no sub-tile of its own --
             tcoop = nsub - 1;                                  // the last wave's partial starts from it (wave 0 used to walk TWO sub-tiles)
             if (wave == nwaves - 1 && Ms[tail0] != 0) {
                 m = a3_tail_dot(Ks, tcoop, 0, qf, lane) * scale2;
@@ -272,28 +297,35 @@ __global__ __launch_bounds__(576) XC_FOUR_WAVES_PER_SIMD void attn3_fwd_kernel(A
     }
     if (coop) {
 #pragma unroll
-        for (int kb = 0; kb < 4; ++kb) qf[kb] = ld16(Qb + (long)qld * ldq + kb * 16 + h * 8);
+        for (int kb = 0; kb < 4; ++kb) qf[kb] = ld16(u.Q + (long)qld * ldq + kb * 16 + h * 8);
     }
 #pragma unroll
     for (int db = 0; db < 2; ++db)
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
     float m = ATT_NEG, l = 0.f;
-    int tend = nsub;
-    if (a3_single_tail(n, p.chunks)) {                         // (uniform) the 257th key first: it initialises (m, l, O) -- see a3_tail_dot
-        tend = nsub - 1;
-        if (!CAUSAL && Ms[tail0] != 0) {                       // (causal: the last key is hidden from every query of a full block)
-            m = a3_tail_dot(Ks, tend, 0, qf, lane) * scale2;
-            l = 1.f;
-            a3_tail_outer(Vs, tend, 0, 1.f, lane, o);
+    if (own) {
+        int tend = nsub;
+        if (a3_single_tail(n, u.abl)) {                        // (uniform) the 257th key first: it initialises (m, l, O) -- see a3_tail_dot
+            tend = nsub - 1;
+            if (!CAUSAL && Ms[tail0] != 0) {                   // (causal: the last key is hidden from every query of a full block)
+                m = a3_tail_dot(Ks, tend, 0, qf, lane) * scale2;
+                l = 1.f;
+                a3_tail_outer(Vs, tend, 0, 1.f, lane, o);
+            }
         }
+        for (int t = 0; t < tend; ++t) a3_fwd_step_auto<CAUSAL>(Ks, Vs, Ms, t, qf, scale2, lane, q0, o, m, l);
     }
-    for (int t = 0; t < tend; ++t) a3_fwd_step_auto<CAUSAL>(Ks, Vs, Ms, t, qf, scale2, lane, q0, o, m, l);
     sync();                                                    // every wave is done with the K / V images (and the tail partials are in)
-    const float inv = l > 0.f ? 1.0f / l : 0.f;
-    a2_store_rows(lds + wave * 32 * 144, o, inv, out, (long)p.heads * ATT_DH, q0, n, lane);
-    if (h == 0 && qrow < n) lse_out[qrow] = m * 0.6931471805599453f + logf(l);    // m is in log2 units
+    // Store bound n: with a cooperative tail the waves that own a block are the n / 32 full ones, so their rows q0 .. q0 + 31 all lie
+    // below tail0 <= n and the bound only ever cuts the ordinary tail of the last block; the tail rows are wave 0's, below.
+    if (own) {
+        const float inv = l > 0.f ? 1.0f / l : 0.f;
+        a2_store_rows(lds + wave * 32 * 144, o, inv, u.out, u.ldo, q0, n, lane);
+        if (h == 0 && qrow < n) u.lse[qrow] = m * 0.6931471805599453f + logf(l);    // m is in log2 units
+    }
     if (coop && wave == 0) {                                   // merge the nwaves partials of every tail row; lane = feature d
+        // (the staging blocks of a2_store_rows lie in [0, nwaves 32 144) of the LDS, the partials behind both images: no overlap)
         for (int q = 0; q < ntail; ++q) {
             float M = ATT_NEG;
             for (int w = 0; w < nwaves; ++w) M = fmaxf(M, Ts[((long)w * A3_TAIL_MAX + q) * A3_TAIL_REC]);
@@ -304,10 +336,26 @@ __global__ __launch_bounds__(576) XC_FOUR_WAVES_PER_SIMD void attn3_fwd_kernel(A
                 L += rec[1] * f;
                 acc += rec[2 + lane] * f;
             }
-            out[(long)(tail0 + q) * p.heads * ATT_DH + lane] = f2bf(L > 0.f ? acc / L : 0.f);
-            if (lane == 0) lse_out[tail0 + q] = M * 0.6931471805599453f + logf(L);
+            u.out[(long)(tail0 + q) * u.ldo + lane] = f2bf(L > 0.f ? acc / L : 0.f);
+            if (lane == 0) u.lse[tail0 + q] = M * 0.6931471805599453f + logf(L);
         }
     }
+}
+// the dense wrapper: unit (bi, hh) owns rows [bi n, bi n + n) and the lse run [batch, heads, n] gives it
+// (at most 128 VGPRs: two 8-wave work-groups of ~78 KB LDS share a CU)
+XC_DEV A3Unit a3_dense_unit(const AttnParams& p) {
+    const int bh = xcd_remap(blockIdx.x, p.batch * p.heads);
+    const int hh = bh % p.heads, bi = bh / p.heads;
+    A3Unit u = a3_unit(reinterpret_cast<const bf16_t*>(p.qkv), reinterpret_cast<const bf16_t*>(p.out), reinterpret_cast<const bf16_t*>(p.dout),
+                       reinterpret_cast<bf16_t*>(p.out), reinterpret_cast<bf16_t*>(p.dqkv), p.lse + ((long)bi * p.heads + hh) * p.n,
+                       (long)bi * p.n, p.n, p.heads, hh);
+    u.mask = p.mask; u.mask_row0 = (long)bi * p.n; u.abl = p.chunks;
+    return u;
+}
+template <bool CAUSAL>
+__global__ __launch_bounds__(576) XC_FOUR_WAVES_PER_SIMD void attn3_fwd_kernel(AttnParams p) {
+    a3_stagger(p.stagger_10ns, p.first_round);
+    a3_fwd_unit<CAUSAL, false>(a3_dense_unit(p), p.scale);
 }
 
 // ---- backward (dQ, dK, dV and delta in one kernel) ------------------------------------------------------------------------
@@ -500,11 +548,13 @@ XC_DEV void a3_row_frags(const bf16_t* X, long ldx, int r, int lane, u32x4 (&f)[
 // rows from global), so the second pair is DMA'd over the first between the phases and a head needs ~80 KB of LDS instead
 // of 160: TWO work-groups of four waves per CU (each wave takes every fourth 32-row block), one computing while the other
 // waits for HBM.  (The one-work-group-per-CU version measured load + store skeleton 405 us, phase A 225, phase B 395, total
-// 1060 = their sum at n = 256.)  p.chunks is a measurement switch here (XCLIP_ATTN_ABL: 1 = skip phase A, 2 = skip phase B, 4 = the tail row as a 33rd block).
+// 1060 = their sum at n = 256.)  u.abl is a measurement switch here (XCLIP_ATTN_ABL: 1 = skip phase A, 2 = skip phase B, 4 = the tail row as a 33rd block).
+// The block loops stride by the launch's wave count, so a launch sized for a longer unit (attention_varlen.h) needs no guard here: a surplus
+// wave finds no block, takes its share of a cooperative tail and meets every barrier.
 template <bool CAUSAL>
-__global__ __launch_bounds__(256) void attn3_bwd_kernel(AttnParams p) {
+XC_DEV void a3_bwd_unit(const A3Unit& u, float scale) {
     XC_LDS_DYNAMIC(lds);
-    const int n = p.n, npad = (n + 31) & ~31;
+    const int n = u.n, npad = (n + 31) & ~31;
     const int img = npad * 128;
     unsigned char* R0 = lds;                                   // K, then Q
     unsigned char* R1 = R0 + img;                              // V, then dO
@@ -514,31 +564,22 @@ __global__ __launch_bounds__(256) void attn3_bwd_kernel(AttnParams p) {
     float* Tp = Ds + npad;                                     // [nwaves][A3_TAIL_MAX][128] tail partials: dQ (phase A), dK | dV (phase B)
     const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, c31 = lane & 31;
     const int wave = uniform(tid >> 6), nwaves = blockDim.x >> 6;
-    a3_stagger(p.stagger_10ns, p.first_round);
-    const int bh = xcd_remap(blockIdx.x, p.batch * p.heads);
-    const int hh = bh % p.heads, bi = bh / p.heads;
-    const long ldq = 3L * p.heads * ATT_DH, ldo = (long)p.heads * ATT_DH;
-    const bf16_t* Qb = reinterpret_cast<const bf16_t*>(p.qkv) + (long)bi * n * ldq + hh * ATT_DH;
-    const bf16_t* Kb = Qb + (long)p.heads * ATT_DH;
-    const bf16_t* Vb = Kb + (long)p.heads * ATT_DH;
-    const bf16_t* dOb = reinterpret_cast<const bf16_t*>(p.dout) + (long)bi * n * ldo + hh * ATT_DH;
-    const bf16_t* Ob = reinterpret_cast<const bf16_t*>(p.out) + (long)bi * n * ldo + hh * ATT_DH;
-    bf16_t* dQ = reinterpret_cast<bf16_t*>(p.dqkv) + (long)bi * n * ldq + hh * ATT_DH;
-    bf16_t* dK = dQ + (long)p.heads * ATT_DH;
-    bf16_t* dV = dK + (long)p.heads * ATT_DH;
+    const long ldq = u.ldq, ldo = u.ldo;
+    const bf16_t *Qb = u.Q, *Kb = u.K, *Vb = u.V, *dOb = u.dO, *Ob = u.O;
+    bf16_t *dQ = u.dQ, *dK = u.dK, *dV = u.dV;
     a3_dma_image(R0, Kb, ldq, n, npad, wave, nwaves, lane);
     a3_dma_image(R1, Vb, ldq, n, npad, wave, nwaves, lane);
-    a3_key_validity(Ms, p.mask, (long)bi * n, n, npad);
+    a3_key_validity(Ms, u.mask, u.mask_row0, n, npad);
     const bool coop = a3_coop_tail(n);
     const int tail0 = (n >> 5) << 5, ntail = n & 31;
     const int nblk = a3_waves(n);                              // 32-row blocks owned by single waves (without a cooperative tail)
     const int nsub = npad >> 5;
-    const float scale2 = p.scale * 1.4426950408889634f;
+    const float scale2 = scale * 1.4426950408889634f;
     // delta_i = sum_d dO[i, d] O[i, d] and lse_i log2(e): lane (i = c31, half h) covers 32 of the 64 d
     for (int blk = wave; blk < nsub; blk += nwaves) {
         const int row_ = blk * 32 + c31;
         const int rl = row_ < n ? row_ : n - 1;
-        const float lse_r = p.lse[((long)bi * p.heads + hh) * n + rl];      // (unconditional, with the row's O / dO chunks: one round trip)
+        const float lse_r = u.lse[rl];                                      // (unconditional, with the row's O / dO chunks: one round trip)
         float acc = 0.f;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -562,7 +603,7 @@ __global__ __launch_bounds__(256) void attn3_bwd_kernel(AttnParams p) {
     // ---- phase A: dQ^T[d, query] for the wave's query blocks, streaming the key sub-tiles of the K / V images ----
     u32x4 f0[4], f1[4];                                        // the block's own rows: (Q, dO) in phase A, (K, V) in phase B
     f32x16 g0[2], g1[2];                                       // dQ in phase A; dK, dV in phase B
-    if (!(p.chunks & 1)) {
+    if (!(u.abl & 1)) {
         if (coop) {                                            // tail queries first: this wave's share of the key sub-tiles
             const int trow = tail0 + c31 < n ? tail0 + c31 : n - 1;
             a3_row_frags(Qb, ldq, trow, lane, f0);
@@ -573,7 +614,7 @@ __global__ __launch_bounds__(256) void attn3_bwd_kernel(AttnParams p) {
                 for (int r = 0; r < 16; ++r) g0[db][r] = 0.f;
             const float lq = Ls[tail0 + c31], dl = Ds[tail0 + c31];
             int tcoop = nsub;
-            if (a3_single_tail(n, p.chunks)) {                 // (uniform) tail query x tail key: the last wave's partial starts from it
+            if (a3_single_tail(n, u.abl)) {                   // (uniform) tail query x tail key: the last wave's partial starts from it
                 tcoop = nsub - 1;
                 const float st = a3_tail_dot(R0, tcoop, 0, f0, lane), dt_ = a3_tail_dot(R1, tcoop, 0, f1, lane);
                 if (wave == nwaves - 1 && Ms[tail0] != 0) a3_tail_outer(R0, tcoop, 0, fast_exp2(st * scale2 - lq) * (dt_ - dl), lane, g0);
@@ -592,7 +633,7 @@ __global__ __launch_bounds__(256) void attn3_bwd_kernel(AttnParams p) {
                 for (int r = 0; r < 16; ++r) g0[db][r] = 0.f;
             const float lse_q = Ls[row], delta_q = Ds[row];
             int tend = CAUSAL ? (rb + 1 < nsub ? rb + 1 : nsub) : nsub;            // key sub-tiles above the diagonal contribute nothing
-            if (a3_single_tail(n, p.chunks) && !CAUSAL) {                           // (uniform) the 257th key: dQ starts at dS k_tail
+            if (a3_single_tail(n, u.abl) && !CAUSAL) {                             // (uniform) the 257th key: dQ starts at dS k_tail
                 tend = nsub - 1;
                 if (Ms[tail0] != 0) {
                     const float pt = fast_exp2(a3_tail_dot(R0, tend, 0, f0, lane) * scale2 - lse_q);
@@ -601,24 +642,24 @@ __global__ __launch_bounds__(256) void attn3_bwd_kernel(AttnParams p) {
                 }
             }
             a3_bwd_dq_sweep<CAUSAL>(R0, R1, Ms, 0, tend, 1, plain_bits, f0, f1, lse_q, delta_q, scale2, lane, row, g0);
-            a3_store_rows_direct(g0, dQ, ldq, rb * 32, n, lane, p.scale);
+            a3_store_rows_direct(g0, dQ, ldq, rb * 32, n, lane, scale);    // (bound n: a block below a cooperative tail ends at tail0 <= n, as in the forward)
         }
     }
     sync();                                                    // every wave is done with the K / V images; the tail partials are complete
     a3_dma_image(R0, Qb, ldq, n, npad, wave, nwaves, lane);
     a3_dma_image(R1, dOb, ldo, n, npad, wave, nwaves, lane);
-    if (coop && wave == 0 && !(p.chunks & 1)) {                // tail dQ = sum of the waves' partials; lane = feature d
+    if (coop && wave == 0 && !(u.abl & 1)) {                  // tail dQ = sum of the waves' partials; lane = feature d
         for (int q = 0; q < ntail; ++q) {
             float acc = 0.f;
             for (int w = 0; w < nwaves; ++w) acc += Tp[((long)w * A3_TAIL_MAX + q) * 128 + lane];
-            dQ[(long)(tail0 + q) * ldq + lane] = f2bf(acc * p.scale);
+            dQ[(long)(tail0 + q) * ldq + lane] = f2bf(acc * scale);
         }
     }
     wait_vmem();
     sync();                                                    // Q / dO images in place; Tp may be reused
 
     // ---- phase B: dK^T, dV^T for the wave's key blocks, streaming the query sub-tiles of the Q / dO images ----
-    if (!(p.chunks & 2)) {
+    if (!(u.abl & 2)) {
         for (int rb = wave; rb < nblk; rb += nwaves) {
             const int row = rb * 32 + c31;
             const int rl = row < n ? row : n - 1;
@@ -631,7 +672,7 @@ __global__ __launch_bounds__(256) void attn3_bwd_kernel(AttnParams p) {
                 for (int r = 0; r < 16; ++r) { g0[db][r] = 0.f; g1[db][r] = 0.f; }
             const bool keys_plain = wave_all(kvalid);                              // (uniform: no padding among this block's keys)
             int qend = nsub;
-            if (a3_single_tail(n, p.chunks)) {                                     // (uniform) the 257th query: dK / dV start at its contribution
+            if (a3_single_tail(n, u.abl)) {                                       // (uniform) the 257th query: dK / dV start at its contribution
                 qend = nsub - 1;                                                   // (causal: the last query sees every key)
                 const float st = a3_tail_dot(R0, qend, 0, f0, lane);               // (every lane: the dot product ends in a cross-lane exchange)
                 const float pt = kvalid ? fast_exp2(st * scale2 - Ls[tail0]) : 0.f;
@@ -641,7 +682,7 @@ __global__ __launch_bounds__(256) void attn3_bwd_kernel(AttnParams p) {
             }
             // (query sub-tiles below the diagonal see none of these keys)
             a3_bwd_dkv_sweep<CAUSAL>(R0, R1, Ls, Ds, CAUSAL ? rb : 0, qend, 1, n, keys_plain, f0, f1, kvalid, scale2, lane, row, g0, g1);
-            a3_store_rows_direct(g0, dK, ldq, rb * 32, n, lane, p.scale);
+            a3_store_rows_direct(g0, dK, ldq, rb * 32, n, lane, scale);
             a3_store_rows_direct(g1, dV, ldq, rb * 32, n, lane);
         }
         if (coop) {                                            // tail keys: this wave's share of the query sub-tiles
@@ -654,7 +695,7 @@ __global__ __launch_bounds__(256) void attn3_bwd_kernel(AttnParams p) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) { g0[db][r] = 0.f; g1[db][r] = 0.f; }
             int tcoop = nsub;
-            if (a3_single_tail(n, p.chunks)) {                 // (uniform) tail key x tail query: the last wave's partial starts from it
+            if (a3_single_tail(n, u.abl)) {                   // (uniform) tail key x tail query: the last wave's partial starts from it
                 tcoop = nsub - 1;
                 const float st = a3_tail_dot(R0, tcoop, 0, f0, lane), dt_ = a3_tail_dot(R1, tcoop, 0, f1, lane);
                 if (wave == nwaves - 1) {
@@ -673,7 +714,7 @@ __global__ __launch_bounds__(256) void attn3_bwd_kernel(AttnParams p) {
     }
     if (coop) {
         sync();
-        if (wave == 0 && !(p.chunks & 2)) {
+        if (wave == 0 && !(u.abl & 2)) {
             for (int q = 0; q < ntail; ++q) {
                 float ak = 0.f, av = 0.f;
                 for (int w = 0; w < nwaves; ++w) {
@@ -681,11 +722,16 @@ __global__ __launch_bounds__(256) void attn3_bwd_kernel(AttnParams p) {
                     ak += rec[lane];
                     av += rec[64 + lane];
                 }
-                dK[(long)(tail0 + q) * ldq + lane] = f2bf(ak * p.scale);
+                dK[(long)(tail0 + q) * ldq + lane] = f2bf(ak * scale);
                 dV[(long)(tail0 + q) * ldq + lane] = f2bf(av);
             }
         }
     }
+}
+template <bool CAUSAL>
+__global__ __launch_bounds__(256) void attn3_bwd_kernel(AttnParams p) {
+    a3_stagger(p.stagger_10ns, p.first_round);
+    a3_bwd_unit<CAUSAL>(a3_dense_unit(p), p.scale);
 }
 
 constexpr int A3_BWD_WAVES = 4;
@@ -696,9 +742,11 @@ inline int attn3_fwd_lds_bytes(int n) {
     const int a = 2 * npad * 128 + npad + nw * A3_TAIL_MAX * A3_TAIL_REC * 4, b = nw * 32 * 144;
     return (a > b ? a : b) + 64;
 }
-inline int attn3_bwd_lds_bytes(int n) {
+// tail_partials: carve Tp behind the per-query arrays (a launch of exactly n rows needs it only under a cooperative tail)
+inline int a3_bwd_lds_bytes(int n, bool tail_partials) {
     const int npad = (n + 31) & ~31;
-    return 2 * npad * 128 + npad + 2 * npad * 4 + (a3_coop_tail(n) ? a3_bwd_waves(n) * A3_TAIL_MAX * 128 * 4 : 0) + 64;
+    return 2 * npad * 128 + npad + 2 * npad * 4 + (tail_partials ? a3_bwd_waves(n) * A3_TAIL_MAX * 128 * 4 : 0) + 64;
 }
+inline int attn3_bwd_lds_bytes(int n) { return a3_bwd_lds_bytes(n, a3_coop_tail(n)); }
 
 }  // namespace xc

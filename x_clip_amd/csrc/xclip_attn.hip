@@ -111,19 +111,20 @@ int attn_setup(const char* fn, const AttnCall& c, bool ptrs_aligned, AttnParams&
 #undef XC_REQ
 }
 
-// ---- one query row per (sample, head): the last layer of a tower whose caller reads a single token row (kernels/attention_pool.h) ----
-template <typename T>
-int launch_attn_pool(const AttnPoolParams& p, int64_t head_dim, bool backward, hipStream_t st) {
-    const dim3 grid((unsigned)(((int64_t)p.batch * p.heads + 3) / 4)), block(256);
-    if (head_dim == 64) {
-        if (backward) hipLaunchKernelGGL((attn_pool_bwd_kernel<T, 64>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((attn_pool_fwd_kernel<T, 64>), grid, block, 0, st, p);
-    } else {
-        if (backward) hipLaunchKernelGGL((attn_pool_bwd_kernel<T, 128>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((attn_pool_fwd_kernel<T, 128>), grid, block, 0, st, p);
-    }
-    return 0;
+// ---- the one-wave-per-unit kernel families (kernels/attention_pool.h: dense and packed pooled; kernels/attention_varlen.h: plain) ----
+// F<T, HS>::fwd / ::bwd are the family's kernels; four waves to a work-group, `units` waves in all
+template <template <typename, int> class F, typename T, typename P>
+void launch_wave_per_unit(const P& p, int64_t units, int64_t head_dim, bool backward, hipStream_t st) {
+    const dim3 grid((unsigned)((units + 3) / 4)), block(256);
+    if (head_dim == 64) hipLaunchKernelGGL((backward ? F<T, 64>::bwd : F<T, 64>::fwd), grid, block, 0, st, p);
+    else hipLaunchKernelGGL((backward ? F<T, 128>::bwd : F<T, 128>::fwd), grid, block, 0, st, p);
 }
+#define XC_WAVE_FAMILY(NAME, PARAMS, FWD, BWD) \
+    template <typename T, int HS> struct NAME { static constexpr void (*fwd)(PARAMS) = FWD<T, HS>; static constexpr void (*bwd)(PARAMS) = BWD<T, HS>; }
+XC_WAVE_FAMILY(PoolKernels, AttnPoolParams, attn_pool_fwd_kernel, attn_pool_bwd_kernel);
+XC_WAVE_FAMILY(PoolVarlenKernels, AttnPoolVarlenParams, attn_pool_varlen_fwd_kernel, attn_pool_varlen_bwd_kernel);
+XC_WAVE_FAMILY(VarlenPlainKernels, AttnVarlenParams, attn_varlen_plain_fwd_kernel, attn_varlen_plain_bwd_kernel);
+#undef XC_WAVE_FAMILY
 }  // namespace
 
 extern "C" {
@@ -280,7 +281,7 @@ int xclip_attention_pool_fwd(const void* q, const void* kv, const uint8_t* mask,
     memset(&p, 0, sizeof(p));
     p.q = q; p.kv = kv; p.mask = mask; p.out = out; p.lse = lse;
     p.batch = (int)batch; p.n = (int)n; p.heads = (int)heads; p.nvis = (int)visible_keys; p.scale = scale;
-    by_dtype(dtype, [&](auto t) { launch_attn_pool<typename decltype(t)::type>(p, head_dim, false, (hipStream_t)stream); });
+    by_dtype(dtype, [&](auto t) { launch_wave_per_unit<PoolKernels, typename decltype(t)::type>(p, batch * heads, head_dim, false, (hipStream_t)stream); });
     return check_launch(__func__);
 }
 
@@ -297,7 +298,7 @@ int xclip_attention_pool_bwd(const void* q, const void* kv, const uint8_t* mask,
     memset(&p, 0, sizeof(p));
     p.q = q; p.kv = kv; p.mask = mask; p.out = const_cast<void*>(out); p.lse = const_cast<float*>(lse); p.dout = dout; p.dq = dq; p.dkv = dkv;
     p.batch = (int)batch; p.n = (int)n; p.heads = (int)heads; p.nvis = (int)visible_keys; p.scale = scale;
-    by_dtype(dtype, [&](auto t) { launch_attn_pool<typename decltype(t)::type>(p, head_dim, true, (hipStream_t)stream); });
+    by_dtype(dtype, [&](auto t) { launch_wave_per_unit<PoolKernels, typename decltype(t)::type>(p, batch * heads, head_dim, true, (hipStream_t)stream); });
     return check_launch(__func__);
 }
 
@@ -322,17 +323,6 @@ static int attn_varlen_setup(const char* fn, const void* qkv, const int32_t* cu,
 static inline bool attn_varlen_resident(int dtype, int64_t head_dim, int64_t max_len) {
     return dtype == XCLIP_BF16 && head_dim == 64 && max_len <= xc::A3_MAX_N;
 }
-template <typename T>
-static void launch_attn_varlen_plain(const xc::AttnVarlenParams& p, int64_t head_dim, bool backward, hipStream_t st) {
-    const dim3 grid((unsigned)(((int64_t)p.rows * p.heads + 3) / 4)), block(256);
-    if (head_dim == 64) {
-        if (backward) hipLaunchKernelGGL((xc::attn_varlen_plain_bwd_kernel<T, 64>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((xc::attn_varlen_plain_fwd_kernel<T, 64>), grid, block, 0, st, p);
-    } else {
-        if (backward) hipLaunchKernelGGL((xc::attn_varlen_plain_bwd_kernel<T, 128>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((xc::attn_varlen_plain_fwd_kernel<T, 128>), grid, block, 0, st, p);
-    }
-}
 
 extern "C" {
 
@@ -350,7 +340,7 @@ int xclip_attention_varlen_fwd(const void* qkv, const int32_t* cu, void* out, fl
         XC_ALLOW_LDS(attn_varlen_fwd_kernel, 160 * 1024);
         hipLaunchKernelGGL(attn_varlen_fwd_kernel, dim3((unsigned)(batch * heads)), dim3(attn_varlen_fwd_waves((int)max_len) * 64), lds, st, p);
     } else {
-        by_dtype(dtype, [&](auto t) { launch_attn_varlen_plain<typename decltype(t)::type>(p, head_dim, false, st); });
+        by_dtype(dtype, [&](auto t) { launch_wave_per_unit<VarlenPlainKernels, typename decltype(t)::type>(p, rows * heads, head_dim, false, st); });
     }
     return check_launch(__func__);
 }
@@ -370,7 +360,7 @@ int xclip_attention_varlen_bwd(const void* qkv, const int32_t* cu, const void* o
         XC_ALLOW_LDS(attn_varlen_bwd_kernel, 160 * 1024);
         hipLaunchKernelGGL(attn_varlen_bwd_kernel, dim3((unsigned)(batch * heads)), dim3(attn_varlen_bwd_waves((int)max_len) * 64), lds, st, p);
     } else {
-        by_dtype(dtype, [&](auto t) { launch_attn_varlen_plain<typename decltype(t)::type>(p, head_dim, true, st); });
+        by_dtype(dtype, [&](auto t) { launch_wave_per_unit<VarlenPlainKernels, typename decltype(t)::type>(p, rows * heads, head_dim, true, st); });
     }
     return check_launch(__func__);
 }
@@ -389,17 +379,6 @@ static int attn_pool_varlen_setup(const char* fn, int64_t rows, int64_t batch, i
     return 0;
 #undef XC_REQ
 }
-template <typename T>
-static void launch_attn_pool_varlen(const xc::AttnPoolVarlenParams& p, int64_t head_dim, bool backward, hipStream_t st) {
-    const dim3 grid((unsigned)(((int64_t)p.batch * p.heads + 3) / 4)), block(256);
-    if (head_dim == 64) {
-        if (backward) hipLaunchKernelGGL((xc::attn_pool_varlen_bwd_kernel<T, 64>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((xc::attn_pool_varlen_fwd_kernel<T, 64>), grid, block, 0, st, p);
-    } else {
-        if (backward) hipLaunchKernelGGL((xc::attn_pool_varlen_bwd_kernel<T, 128>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((xc::attn_pool_varlen_fwd_kernel<T, 128>), grid, block, 0, st, p);
-    }
-}
 
 extern "C" {
 
@@ -413,7 +392,7 @@ int xclip_attention_pool_varlen_fwd(const void* q, const void* kv, const int32_t
     memset(&p, 0, sizeof(p));
     p.q = q; p.kv = kv; p.cu = cu; p.out = out; p.lse = lse;
     p.batch = (int)batch; p.heads = (int)heads; p.rows = (int)rows; p.scale = scale;
-    by_dtype(dtype, [&](auto t) { launch_attn_pool_varlen<typename decltype(t)::type>(p, head_dim, false, (hipStream_t)stream); });
+    by_dtype(dtype, [&](auto t) { launch_wave_per_unit<PoolVarlenKernels, typename decltype(t)::type>(p, batch * heads, head_dim, false, (hipStream_t)stream); });
     return check_launch(__func__);
 }
 
@@ -428,7 +407,7 @@ int xclip_attention_pool_varlen_bwd(const void* q, const void* kv, const int32_t
     memset(&p, 0, sizeof(p));
     p.q = q; p.kv = kv; p.cu = cu; p.out = const_cast<void*>(out); p.lse = const_cast<float*>(lse); p.dout = dout; p.dq = dq; p.dkv = dkv;
     p.batch = (int)batch; p.heads = (int)heads; p.rows = (int)rows; p.scale = scale;
-    by_dtype(dtype, [&](auto t) { launch_attn_pool_varlen<typename decltype(t)::type>(p, head_dim, true, (hipStream_t)stream); });
+    by_dtype(dtype, [&](auto t) { launch_wave_per_unit<PoolVarlenKernels, typename decltype(t)::type>(p, batch * heads, head_dim, true, (hipStream_t)stream); });
     return check_launch(__func__);
 }
 
