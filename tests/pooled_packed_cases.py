@@ -1,5 +1,5 @@
 """Shared cases of the packed text tower's pooled last layer (CLIP.pack_text_pool_last): the one-query varlen attention kernels
-(csrc/kernels/attention_pool_varlen.h) and xclip_rows_add_at against fp64 / bit references, and the public interface end to end.
+(csrc/kernels/attention_pool.h, the packed wrappers) and xclip_rows_add_at against fp64 / bit references, and the public interface end to end.
 tests/test_pooled_packed_emu.py runs them on the CPU emulator build, tests/test_pooled_packed_gpu.py on an MI355X.
 
 Bars: the kernels hold kernel_cases.case_attention_pool's (out 2 bf16 ulps of the scale / 2e-5, lse the fp32 bar, dq / dkv 2 ulps / 6e-5); end to end
@@ -143,6 +143,27 @@ def case_pool_varlen_equals_dense_pool_bits(dev, dtype, n, slot, B=3, heads=3):
     d_dq, d_dkv = ops.attention_pool_bwd(q, kv.view(B, n, -1), None, d_out, dout, d_lse, heads, scale, slot)
     for name, a, b in zip(("out", "lse", "dq", "dkv"), got, (d_out, d_lse, d_dq, d_dkv.view(B * n, -1))):
         assert torch.equal(P._bits(a), P._bits(b)), f"{name}: packed and dense pooled differ in bits at n {n} slot {slot}"
+
+
+PLAIN_ROUTES = ((F32, 64), (F32, 128), (BF16, 128))       # (dtype, slot) that xclip_attention_varlen_* sends to its plain one-wave-per-row kernels
+LENS_PLAIN = LENS_KPL + (70,)                             # a one-key unit, partial loads, a whole load plus one, several loads
+
+
+def case_plain_varlen_equals_pool_varlen_bits(dev, dtype, slot, lens=LENS_PLAIN, heads=3):
+    """the plain varlen kernels (packed_cases.varlen_launch, every row a query) and the pooled varlen kernels (the samples' first rows as the
+    queries) run ONE key sweep (attention_pool.h ap_fwd_unit / ap_bwd_unit) over the same keys in the same order: on the same packed qkv, with
+    dout zero off the first rows, out / lse / dq of the first rows bit for bit.  dK / dV are not compared: the plain kernel sums them over the
+    sample's queries."""
+    assert (dtype, slot) in PLAIN_ROUTES
+    qkv, q, kv, dout = pool_varlen_data(lens, heads, slot, slot, dtype, dev, seed=4)
+    scale, cu, inner = slot ** -0.5, P._cu(lens, dev), heads * slot
+    first = cu[:-1].long()
+    dout_rows = torch.zeros(qkv.shape[0], inner, dtype=dtype, device=dev)
+    dout_rows[first] = dout
+    out, lse, dqkv = P.varlen_launch(qkv, dout_rows, cu, max(lens), heads, slot, scale)
+    p_out, p_lse, p_dq, _ = pool_varlen_launch(q, kv, dout, cu, heads, slot, scale)
+    for name, a, b in (("out", out[first], p_out), ("lse", lse[:, first].t(), p_lse), ("dq", dqkv[first, :inner], p_dq)):
+        assert torch.equal(P._bits(a), P._bits(b)), f"{name}: plain and pooled varlen differ in bits at slot {slot} {dtype}"
 
 
 def case_pool_varlen_full(dev, dtype=BF16, samples=256, heads=8, slot=64, repeats=3):

@@ -57,6 +57,11 @@ def test_pool_varlen_equals_dense_pool_bit_for_bit(n, slot, dtype):
     Q.case_pool_varlen_equals_dense_pool_bits(DEV, dtype, n, slot)
 
 
+@pytest.mark.parametrize("dtype,slot", Q.PLAIN_ROUTES, ids=["fp32_slot64", "fp32_slot128", "bf16_slot128"])
+def test_plain_varlen_equals_pool_varlen_bit_for_bit(dtype, slot):
+    Q.case_plain_varlen_equals_pool_varlen_bits(DEV, dtype, slot)
+
+
 @DTYPES
 @pytest.mark.parametrize("strided", [False, True], ids=["contiguous", "strided"])
 def test_rows_add_at(strided, dtype):

@@ -15,9 +15,12 @@
 //     kernels run too -- only the unit's row range differs, read from cu here instead of computed from (sample, n).  K / V (backward: then
 //     Q / dO) of the (sample, head) unit are DMA'd into LDS once and swept with MFMA.
 //     The launch is sized by max_len (waves, LDS); a unit shorter than that leaves its surplus waves at the barriers only.
-//   * plain (fp32, HS = 128, max_len > A3_MAX_N): one wave per (row, head), attention_pool.h's wave-wide key loads and online softmax with
-//     that row as the query; the backward's wave takes its row first as a query (dQ) and then as a key (dK, dV: the sample's queries
-//     stream past it).  O(len) work per row, L2-resident re-reads: a correctness path, not a fast one.
+//   * plain (fp32, HS = 128, max_len > A3_MAX_N): one wave per (row, head), attention_pool.h's key sweep (ap_fwd_unit / ap_bwd_unit)
+//     with that row as the query of its sample's keys (the pooled kernels run them too: for a sample's first row the two give
+//     the same out, lse and dQ bits, tests/pooled_packed_cases.py case_plain_varlen_equals_pool_varlen_bits).  The forward is a wrapper
+//     around ap_fwd_unit; the backward's wave takes its row first as a query (dQ: a copy of ap_bwd_unit's loop, see the kernel) and then as
+//     a key (dK, dV: the sample's queries stream past it -- another loop, three loads per row).  O(len) work per row, L2-resident
+//     re-reads: a correctness path, not a fast one.
 #pragma once
 #include "attention3.h"
 #include "attention_pool.h"
@@ -43,58 +46,31 @@ XC_DEV int av_sample_of(const int* cu, int batch, int r) {
     return lo;
 }
 
+// the unit of wave blockIdx.x * 4 + wave_id(): row r of head h as the QUERY of its own sample's keys, all of them visible; false: the wave
+// is past the last unit and leaves whole (no barriers anywhere).  attention_pool.h's ApUnit with K / V in the same array as the query
 template <typename T, int HS>
-__global__ __launch_bounds__(256) void attn_varlen_plain_fwd_kernel(AttnVarlenParams p) {
-    constexpr int VEC = Elem<T>::VEC, CH = HS / VEC, KPL = 64 / CH;
-    static_assert(CH >= 1 && CH <= 64 && (CH & (CH - 1)) == 0, "chunks per key row must be a power of two");
-    const int lane = lane_id();
+XC_DEV bool av_plain_unit(const AttnVarlenParams& p, ApUnit<T>& u) {
     const long unit = (long)blockIdx.x * 4 + wave_id();
-    if (unit >= (long)p.rows * p.heads) return;                // whole wave leaves; no barriers below
+    if (unit >= (long)p.rows * p.heads) return false;
     const int r = (int)(unit / p.heads), h = (int)(unit % p.heads);
     const int s = av_sample_of(p.cu, p.batch, r);
-    const int k0 = p.cu[s], k1 = p.cu[s + 1];
-    const int inner = p.heads * HS;
-    const long ldq = 3L * inner;
-    const int g = lane / CH, c = lane % CH;                    // key within the wave-wide load, 16-byte chunk of its row
-    const T* base = static_cast<const T*>(p.qkv) + (long)h * HS + c * VEC;
-    float qv[VEC];
-    load_vec<T>(base + (long)r * ldq, qv);
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) qv[e] *= p.scale;
-    float m = -INFINITY, l = 0.f, acc[VEC];
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) acc[e] = 0.f;
-    for (int j0 = k0; j0 < k1; j0 += KPL) {
-        const int j = j0 + g;
-        const bool live = j < k1;
-        const int jr = live ? j : k1 - 1;                      // (past the sample's end: a valid address, the value is not used)
-        float kf[VEC], vf[VEC];
-        load_vec<T>(base + (long)jr * ldq + inner, kf);
-        load_vec<T>(base + (long)jr * ldq + 2 * inner, vf);
-        float part = 0.f;
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) part += qv[e] * kf[e];
-        const float sc = group_sum<CH>(part);
-        if (live) {                                            // (uniform over the CH lanes of a key)
-            const float mn = fmaxf(m, sc);
-            const float fac = fast_exp(m - mn), pj = fast_exp(sc - mn);
-            l = l * fac + pj;
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) acc[e] = acc[e] * fac + pj * vf[e];
-            m = mn;
-        }
-    }
-    const float mt = cross_max<CH>(m);                         // merge the KPL groups: a group that saw no key has m = -inf, l = 0
-    const float w = (m == -INFINITY) ? 0.f : fast_exp(m - mt);
-    const float lt = cross_sum<CH>(l * w);
-    const float inv = lt > 0.f ? 1.f / lt : 0.f;
-    float o[VEC];
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) o[e] = cross_sum<CH>(acc[e] * w) * inv;
-    if (g == 0) store_vec<T>(static_cast<T*>(p.out) + (long)r * inner + (long)h * HS + c * VEC, o);
-    if (lane == 0) p.lse[(long)h * p.rows + r] = mt + logf(lt);
+    const int inner = p.heads * HS, k0 = p.cu[s], k1 = p.cu[s + 1];
+    const long ldq = 3L * inner, at = (long)r * inner + (long)h * HS;
+    const T* qkv = static_cast<const T*>(p.qkv) + (long)h * HS;
+    T* dqkv = static_cast<T*>(p.dqkv) + (long)h * HS;
+    u = {qkv + r * ldq, static_cast<const T*>(p.dout) + at, static_cast<T*>(p.out) + at, p.lse + (long)h * p.rows + r,
+         qkv + inner, ldq, inner, nullptr, k0, k1, k1, dqkv + r * ldq, dqkv + inner};
+    return true;
 }
 
+template <typename T, int HS>
+__global__ __launch_bounds__(256) void attn_varlen_plain_fwd_kernel(AttnVarlenParams p) {
+    ApUnit<T> u;
+    if (av_plain_unit<T, HS>(p, u)) ap_fwd_unit<T, HS>(u, p.scale);
+}
+
+// The query half below is ap_bwd_unit's loop without the dK / dV stores, kept as its own copy: called through the body, the bf16 HS = 128
+// instantiation takes 82 registers instead of 80 and falls from 6 to 5 waves per SIMD (measured 5 % slower; profiles/r19_pool_one_loop_*).
 template <typename T, int HS>
 __global__ __launch_bounds__(256) void attn_varlen_plain_bwd_kernel(AttnVarlenParams p) {
     constexpr int VEC = Elem<T>::VEC, CH = HS / VEC, KPL = 64 / CH;

@@ -13,7 +13,6 @@
 #include "kernels/attention6.h"
 #include "kernels/attention7.h"
 #include "kernels/attention_pool.h"
-#include "kernels/attention_pool_varlen.h"
 #include "kernels/attention_varlen.h"
 
 using namespace xc;
@@ -125,6 +124,23 @@ XC_WAVE_FAMILY(PoolKernels, AttnPoolParams, attn_pool_fwd_kernel, attn_pool_bwd_
 XC_WAVE_FAMILY(PoolVarlenKernels, AttnPoolVarlenParams, attn_pool_varlen_fwd_kernel, attn_pool_varlen_bwd_kernel);
 XC_WAVE_FAMILY(VarlenPlainKernels, AttnVarlenParams, attn_varlen_plain_fwd_kernel, attn_varlen_plain_bwd_kernel);
 #undef XC_WAVE_FAMILY
+
+// ---- one query row per (sample, head) (kernels/attention_pool.h) ----
+// the common checks and fields of the dense pair; ptr_err: the entry point's own pointer complaint, or null; -> 0, or 1 with the error recorded
+// under `fn`.  An empty batch passes every check (the caller returns 0)
+int attn_pool_setup(const char* fn, const void* q, const void* kv, const uint8_t* mask, int64_t batch, int64_t n, int64_t heads, int64_t head_dim,
+                    float scale, int64_t visible_keys, int dtype, const char* ptr_err, AttnPoolParams& p) {
+#define XC_REQ(cond, msg) do { if (!(cond)) return xcapi::fail(fn, msg); } while (0)
+    XC_REQ(dtype_ok(dtype), "bad dtype");
+    XC_REQ(batch >= 0 && n > 0 && heads > 0 && visible_keys >= 1 && visible_keys <= n, "bad shape");
+    XC_REQ(head_dim == 64 || head_dim == 128, "head_dim must be 64 or 128 (narrower / in-between widths are zero-padded by the caller)");
+    XC_REQ(ptr_err == nullptr, ptr_err);
+    memset(&p, 0, sizeof(p));
+    p.q = q; p.kv = kv; p.mask = mask;
+    p.batch = (int)batch; p.n = (int)n; p.heads = (int)heads; p.nvis = (int)visible_keys; p.scale = scale;
+    return 0;
+#undef XC_REQ
+}
 }  // namespace
 
 extern "C" {
@@ -272,15 +288,12 @@ int xclip_attention_bwd(const void* qkv, const uint8_t* mask, const void* out, c
 
 int xclip_attention_pool_fwd(const void* q, const void* kv, const uint8_t* mask, void* out, float* lse, int64_t batch, int64_t n,
                              int64_t heads, int64_t head_dim, float scale, int64_t visible_keys, int dtype, void* stream) {
-    XC_REQUIRE(dtype_ok(dtype), "bad dtype");
-    XC_REQUIRE(batch >= 0 && n > 0 && heads > 0 && visible_keys >= 1 && visible_keys <= n, "bad shape");
-    XC_REQUIRE(head_dim == 64 || head_dim == 128, "head_dim must be 64 or 128 (narrower / in-between widths are zero-padded by the caller)");
-    XC_REQUIRE(q && kv && out && lse && aligned16(q) && aligned16(kv) && aligned16(out), "pointers must be non-null and 16-byte aligned");
-    if (batch == 0) return 0;
     AttnPoolParams p;
-    memset(&p, 0, sizeof(p));
-    p.q = q; p.kv = kv; p.mask = mask; p.out = out; p.lse = lse;
-    p.batch = (int)batch; p.n = (int)n; p.heads = (int)heads; p.nvis = (int)visible_keys; p.scale = scale;
+    const bool ptrs_ok = q && kv && out && lse && aligned16(q) && aligned16(kv) && aligned16(out);
+    const int rc = attn_pool_setup(__func__, q, kv, mask, batch, n, heads, head_dim, scale, visible_keys, dtype,
+                                   ptrs_ok ? nullptr : "pointers must be non-null and 16-byte aligned", p);
+    if (rc != 0 || batch == 0) return rc;
+    p.out = out; p.lse = lse;
     by_dtype(dtype, [&](auto t) { launch_wave_per_unit<PoolKernels, typename decltype(t)::type>(p, batch * heads, head_dim, false, (hipStream_t)stream); });
     return check_launch(__func__);
 }
@@ -288,16 +301,13 @@ int xclip_attention_pool_fwd(const void* q, const void* kv, const uint8_t* mask,
 int xclip_attention_pool_bwd(const void* q, const void* kv, const uint8_t* mask, const void* out, const void* dout, const float* lse,
                              void* dq, void* dkv, int64_t batch, int64_t n, int64_t heads, int64_t head_dim, float scale,
                              int64_t visible_keys, int dtype, void* stream) {
-    XC_REQUIRE(dtype_ok(dtype), "bad dtype");
-    XC_REQUIRE(batch >= 0 && n > 0 && heads > 0 && visible_keys >= 1 && visible_keys <= n, "bad shape");
-    XC_REQUIRE(head_dim == 64 || head_dim == 128, "head_dim must be 64 or 128 (narrower / in-between widths are zero-padded by the caller)");
-    XC_REQUIRE(q && kv && out && dout && lse && dq && dkv, "null pointer");
-    XC_REQUIRE(aligned16(q) && aligned16(kv) && aligned16(out) && aligned16(dout) && aligned16(dq) && aligned16(dkv), "pointers must be 16-byte aligned");
-    if (batch == 0) return 0;
     AttnPoolParams p;
-    memset(&p, 0, sizeof(p));
-    p.q = q; p.kv = kv; p.mask = mask; p.out = const_cast<void*>(out); p.lse = const_cast<float*>(lse); p.dout = dout; p.dq = dq; p.dkv = dkv;
-    p.batch = (int)batch; p.n = (int)n; p.heads = (int)heads; p.nvis = (int)visible_keys; p.scale = scale;
+    const bool nonnull = q && kv && out && dout && lse && dq && dkv;
+    const bool aligned = aligned16(q) && aligned16(kv) && aligned16(out) && aligned16(dout) && aligned16(dq) && aligned16(dkv);
+    const int rc = attn_pool_setup(__func__, q, kv, mask, batch, n, heads, head_dim, scale, visible_keys, dtype,
+                                   !nonnull ? "null pointer" : !aligned ? "pointers must be 16-byte aligned" : nullptr, p);
+    if (rc != 0 || batch == 0) return rc;
+    p.out = const_cast<void*>(out); p.lse = const_cast<float*>(lse); p.dout = dout; p.dq = dq; p.dkv = dkv;
     by_dtype(dtype, [&](auto t) { launch_wave_per_unit<PoolKernels, typename decltype(t)::type>(p, batch * heads, head_dim, true, (hipStream_t)stream); });
     return check_launch(__func__);
 }
@@ -367,8 +377,10 @@ int xclip_attention_varlen_bwd(const void* qkv, const int32_t* cu, const void* o
 
 }  // extern "C"
 
-// ---- one query row per (sample, head) over samples of different lengths (kernels/attention_pool_varlen.h) ----
-static int attn_pool_varlen_setup(const char* fn, int64_t rows, int64_t batch, int64_t heads, int64_t head_dim, float scale, int dtype, bool ptrs_ok) {
+// ---- one query row per (sample, head) over samples of different lengths (kernels/attention_pool.h, the packed wrappers) ----
+// the common checks and fields of both entry points; -> 0, or 1 with the error recorded under `fn`
+static int attn_pool_varlen_setup(const char* fn, const void* q, const void* kv, const int32_t* cu, int64_t rows, int64_t batch, int64_t heads,
+                                  int64_t head_dim, float scale, int dtype, bool ptrs_ok, xc::AttnPoolVarlenParams& p) {
 #define XC_REQ(cond, msg) do { if (!(cond)) return xcapi::fail(fn, msg); } while (0)
     XC_REQ(xcapi::dtype_ok(dtype), "bad dtype");
     XC_REQ(batch >= 0 && heads > 0 && rows >= 0, "bad shape");
@@ -376,6 +388,9 @@ static int attn_pool_varlen_setup(const char* fn, int64_t rows, int64_t batch, i
     XC_REQ(head_dim == 64 || head_dim == 128, "head_dim must be 64 or 128 (narrower / in-between widths are zero-padded by the caller)");
     XC_REQ(batch == 0 || ptrs_ok, "pointers must be non-null and 16-byte aligned");
     XC_REQ(scale > 0.f, "scale must be positive");
+    memset(&p, 0, sizeof(p));
+    p.q = q; p.kv = kv; p.cu = cu;
+    p.batch = (int)batch; p.heads = (int)heads; p.rows = (int)rows; p.scale = scale;
     return 0;
 #undef XC_REQ
 }
@@ -385,13 +400,11 @@ extern "C" {
 int xclip_attention_pool_varlen_fwd(const void* q, const void* kv, const int32_t* cu, void* out, float* lse, int64_t rows, int64_t batch,
                                     int64_t heads, int64_t head_dim, float scale, int dtype, void* stream) {
     // (kv may be null when no sample owns a row: nothing is read through it then)
-    const int rc = attn_pool_varlen_setup(__func__, rows, batch, heads, head_dim, scale, dtype,
-                                          q && (kv || rows == 0) && cu && out && lse && aligned16(q) && aligned16(kv) && aligned16(out));
-    if (rc != 0 || batch == 0) return rc;
     AttnPoolVarlenParams p;
-    memset(&p, 0, sizeof(p));
-    p.q = q; p.kv = kv; p.cu = cu; p.out = out; p.lse = lse;
-    p.batch = (int)batch; p.heads = (int)heads; p.rows = (int)rows; p.scale = scale;
+    const int rc = attn_pool_varlen_setup(__func__, q, kv, cu, rows, batch, heads, head_dim, scale, dtype,
+                                          q && (kv || rows == 0) && cu && out && lse && aligned16(q) && aligned16(kv) && aligned16(out), p);
+    if (rc != 0 || batch == 0) return rc;
+    p.out = out; p.lse = lse;
     by_dtype(dtype, [&](auto t) { launch_wave_per_unit<PoolVarlenKernels, typename decltype(t)::type>(p, batch * heads, head_dim, false, (hipStream_t)stream); });
     return check_launch(__func__);
 }
@@ -399,14 +412,12 @@ int xclip_attention_pool_varlen_fwd(const void* q, const void* kv, const int32_t
 int xclip_attention_pool_varlen_bwd(const void* q, const void* kv, const int32_t* cu, const void* out, const void* dout, const float* lse,
                                     void* dq, void* dkv, int64_t rows, int64_t batch, int64_t heads, int64_t head_dim, float scale, int dtype,
                                     void* stream) {
-    const int rc = attn_pool_varlen_setup(__func__, rows, batch, heads, head_dim, scale, dtype,
-                                          q && ((kv && dkv) || rows == 0) && cu && out && dout && lse && dq && aligned16(q) && aligned16(kv) &&
-                                              aligned16(out) && aligned16(dout) && aligned16(dq) && aligned16(dkv));
-    if (rc != 0 || batch == 0) return rc;
     AttnPoolVarlenParams p;
-    memset(&p, 0, sizeof(p));
-    p.q = q; p.kv = kv; p.cu = cu; p.out = const_cast<void*>(out); p.lse = const_cast<float*>(lse); p.dout = dout; p.dq = dq; p.dkv = dkv;
-    p.batch = (int)batch; p.heads = (int)heads; p.rows = (int)rows; p.scale = scale;
+    const int rc = attn_pool_varlen_setup(__func__, q, kv, cu, rows, batch, heads, head_dim, scale, dtype,
+                                          q && ((kv && dkv) || rows == 0) && cu && out && dout && lse && dq && aligned16(q) && aligned16(kv) &&
+                                              aligned16(out) && aligned16(dout) && aligned16(dq) && aligned16(dkv), p);
+    if (rc != 0 || batch == 0) return rc;
+    p.out = const_cast<void*>(out); p.lse = const_cast<float*>(lse); p.dout = dout; p.dq = dq; p.dkv = dkv;
     by_dtype(dtype, [&](auto t) { launch_wave_per_unit<PoolVarlenKernels, typename decltype(t)::type>(p, batch * heads, head_dim, true, (hipStream_t)stream); });
     return check_launch(__func__);
 }

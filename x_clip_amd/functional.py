@@ -382,7 +382,7 @@ def _layer_backward_pooled(dx2: Tensor, t: LayerTape, W: LayerWeights, need: Lay
 # ---- the same for a packed batch (c.layout): the pooled row is the FIRST row of every sample, row cu[s] of the [R, D] arrays ----------------
 # The rows of a sample are not a fixed stride apart, so the strided views above become gathers (xclip_gather_rows by cu[:-1]) and the two
 # "add into the pooled rows" become xclip_rows_add_at; the one-query attention reads each sample's own keys through cu
-# (attention_pool_varlen.h).  Same algebra and the same rounding points as the dense pooled layer above.
+# (attention_pool.h, the packed wrappers).  Same algebra and the same rounding points as the dense pooled layer above.
 def _layer_forward_pooled_packed(x: Tensor, W: LayerWeights, c: _Pass):
     spec, lay, inner = c.spec, c.layout, c.spec.inner
     (R, D), B, first = x.shape, c.layout.batch, c.layout.cu[:-1]
