@@ -20,7 +20,7 @@ extern "C" {
 #endif
 
 enum { XCLIP_F32 = 0, XCLIP_BF16 = 1 };
-#define XCLIP_ABI_VERSION 32
+#define XCLIP_ABI_VERSION 33
 
 int xclip_abi_version(void);
 const char* xclip_last_error(void);
@@ -242,6 +242,18 @@ int xclip_attention_varlen_fwd(const void* qkv, const int32_t* cu, void* out, fl
 int xclip_attention_varlen_bwd(const void* qkv, const int32_t* cu, const void* out, const void* dout, const float* lse, void* dqkv,
                                int64_t rows, int64_t batch, int64_t heads, int64_t head_dim, int64_t max_len, float scale, int dtype,
                                void* stream);
+/* The same over the same arrays under a CAUSAL mask (the autoregressive text encoder packed up to each sample's first EOS token): key row j
+ * is visible to query row i of the same sample iff j <= i, by packed row index, and to no row of another sample.  A row's lse is over keys
+ * [cu[s], row]; a row always sees itself.  Arguments, layouts, the fully overwritten dqkv, "nothing at or behind row `rows` is written", "no
+ * atomics, a fixed summation order" and "a sample longer than max_len is left unwritten" are those of xclip_attention_varlen_fwd / _bwd, and so
+ * is the routing: bf16 with head_dim 64 and max_len <= 288 runs the head-resident MFMA kernels (the bodies of the dense causal kernels: for
+ * samples of one length n = max_len the results equal xclip_attention_fwd / _bwd with causal = 1 bit for bit), anything else the plain
+ * one-wave-per-(row, head) form with the key sweep cut at the row itself. */
+int xclip_attention_varlen_causal_fwd(const void* qkv, const int32_t* cu, void* out, float* lse, int64_t rows, int64_t batch, int64_t heads,
+                                      int64_t head_dim, int64_t max_len, float scale, int dtype, void* stream);
+int xclip_attention_varlen_causal_bwd(const void* qkv, const int32_t* cu, const void* out, const void* dout, const float* lse, void* dqkv,
+                                      int64_t rows, int64_t batch, int64_t heads, int64_t head_dim, int64_t max_len, float scale, int dtype,
+                                      void* stream);
 /* The one-query attention over samples of DIFFERENT lengths laid end to end -- the last layer of the packed text tower under the CLS head
  * (x_clip.py:708 `enc_text[:, 0]`; Attention.forward x_clip.py:213-245 restricted to that query, under the key-padding mask of x_clip.py:334 on
  * the kept rows only):

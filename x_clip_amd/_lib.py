@@ -64,6 +64,8 @@ _SIGNATURES = {
     "xclip_attention_pool_bwd": (c_int, [P, P, P, P, P, P, P, P, L, L, L, L, F, L, I, P]),
     "xclip_attention_varlen_fwd": (c_int, [P, P, P, P, L, L, L, L, L, F, I, P]),
     "xclip_attention_varlen_bwd": (c_int, [P, P, P, P, P, P, L, L, L, L, L, F, I, P]),
+    "xclip_attention_varlen_causal_fwd": (c_int, [P, P, P, P, L, L, L, L, L, F, I, P]),
+    "xclip_attention_varlen_causal_bwd": (c_int, [P, P, P, P, P, P, L, L, L, L, L, F, I, P]),
     "xclip_attention_pool_varlen_fwd": (c_int, [P, P, P, P, P, L, L, L, L, F, I, P]),
     "xclip_attention_pool_varlen_bwd": (c_int, [P, P, P, P, P, P, P, P, L, L, L, L, F, I, P]),
     "xclip_dropout": (c_int, [P, P, L, F, U, I, P]),
@@ -115,7 +117,7 @@ _SIGNATURES = {
     "xclip_grad_accumulate": (c_int, [P, L, L, I, P, I, P]),
 }
 EXPORTS = tuple(_SIGNATURES)
-ABI_VERSION = 32
+ABI_VERSION = 33
 
 
 def _bind(path: str):

@@ -212,17 +212,23 @@ class TextTransformer(nn.Module):
         """pool_row = r (not a reference keyword): the caller will read row r of every sample's encoding and nothing else -- the result is
         then [b, dim], and the last layer's row-wise part (to_out, feed-forward, norm_out) runs on those rows alone (functional.stack_forward).
         layout (packing.TextLayout of x under its key mask; CLIP.pack_text): the tower runs on the kept rows only and returns the CLS rows [b, dim];
-        with pool_row = 0 its last layer is the pooled one as well (CLIP.pack_text_pool_last)"""
+        with pool_row = 0 its last layer is the pooled one as well (CLIP.pack_text_pool_last).
+        A causal encoder (CLIP.pack_text_causal) takes a layout that ends every sample at its first EOS token (text_layout(eos_id=)) and returns
+        the EOS rows [b, dim] -- what `eos_to_front(...)[:, 0]` reads of the dense encoding; its pooled last layer is asked for with
+        pool_row = "eos" (the row is not a fixed position: 0 keeps meaning position 0)"""
         t = self.transformer
         pos = self.abs_pos_emb.weight if exists(self.abs_pos_emb) else None
         if layout is not None:
             if layout.batch != x.shape[0] or layout.n != x.shape[1]:
                 raise ValueError(f"text_layout was built for a [{layout.batch}, {layout.n}] token batch, the text is {tuple(x.shape)}")
-            if pool_row not in (None, 0):
+            if t.causal:
+                if pool_row not in (None, "eos"):
+                    raise ValueError('a packed causal text tower returns the EOS rows: pool_row is "eos" (the pooled last layer) or None (the dense one)')
+            elif pool_row not in (None, 0):
                 raise ValueError("a packed text tower returns the CLS rows: pool_row is 0 (the pooled last layer) or None (the dense one)")
             return XF.text_encode_packed(layout, self.token_emb.weight, pos, self.cls_token, t.stack_params(),
                                          t.spec(rotary=self.rotary_pos_emb.frequencies(x.device) if exists(self.rotary_pos_emb) else None),
-                                         pool_last=pool_row == 0)
+                                         pool_last=pool_row is not None)
         return XF.text_encode(x, mask, self.token_emb.weight, pos, self.cls_token, t.stack_params(),
                               t.spec(rotary=self.rotary_pos_emb.frequencies(x.device) if exists(self.rotary_pos_emb) else None), pool_row=pool_row)
 
@@ -455,6 +461,10 @@ class CLIP(nn.Module):
         # everything behind it on the CLS rows alone -- what prune_unused_rows does for the dense tower (functional._layer_forward_pooled_packed).
         # Same function; the pooled layer rounds at other points than the dense one, so bf16 results move by ulps.  Off: pack_text as before
         self.pack_text_pool_last = False
+        # opt-in, the same for the autoregressive encoder (text_causal_mask, text_eos_id): the tower runs on the rows up to each sample's FIRST EOS
+        # token that the key mask keeps.  A row behind it is a key of no row that is read, so it is as dead as a padded one; the pooled row is
+        # the last kept row of the sample.  Off: every launch as before (pack_text itself goes on refusing a causal model)
+        self._pack_text_causal = False
         # >1: the text batch runs through the text tower in that many slices, each on its own HIP stream.  The tower alternates
         # MFMA-bound GEMMs with HBM-bound row kernels; with two slices in flight one slice's LayerNorm / GEGLU kernels (no LDS, few
         # registers: they fit on a CU beside a persistent GEMM work-group) run under the other slice's GEMMs.  Encoders are row
@@ -528,6 +538,37 @@ class CLIP(nn.Module):
         if why is not None:
             raise NotImplementedError(f"CLIP.pack_text is not available with {why}")
 
+    @property
+    def pack_text_causal(self) -> bool:
+        return self._pack_text_causal
+
+    @pack_text_causal.setter
+    def pack_text_causal(self, on):
+        if on:
+            self._check_pack_text_causal()
+        self._pack_text_causal = bool(on)
+
+    def _check_pack_text_causal(self):
+        """pack_text_causal is pack_text for the causal encoder alone: any other model is pointed at pack_text, and what reads every row is out"""
+        tt = self.text_transformer
+        if not self.text_causal_mask or not isinstance(tt, TextTransformer):
+            raise ValueError("CLIP.pack_text_causal packs the built-in causal text encoder (text_causal_mask=True, read at text_eos_id); "
+                             "for a CLS-token encoder set CLIP.pack_text")
+        why = None                                              # (use_all_token_embeds / use_mlm: refused with a causal encoder at construction)
+        if self.text_encode_without_mask:
+            why = "text_encode_without_mask (without a key mask the padded rows in front of the EOS are attended to: the kept rows would differ)"
+        elif tt.transformer.training and (tt.transformer.attn_dropout > 0. or tt.transformer.ff_dropout > 0.):
+            why = "attn_dropout / ff_dropout in the text tower (the keep-masks are indexed by dense position)"
+        if why is not None:
+            raise NotImplementedError(f"CLIP.pack_text_causal is not available with {why}")
+
+    def _packed_layout(self, text, text_mask=None):
+        """the layout the packed tower of this model takes for a token batch (device tokens: one read of its row count, packing.text_layout)"""
+        from .packing import text_layout
+        if self._pack_text_causal:
+            return text_layout(text, self.text_pad_id, mask=text_mask, has_cls=False, eos_id=self.text_eos_id)
+        return text_layout(text, self.text_pad_id, mask=text_mask)
+
     # ---- what forward and the one-tower entry points share (x_clip.py:650-715) ----
     def _text_tower_call(self, text, text_mask, cls_row_only, layout=None):
         """-> (args, kwargs) of the text tower.  `cls_row_only`: the caller reads `enc_text[:, 0]` and nothing else (x_clip.py:708) -- the
@@ -538,17 +579,17 @@ class CLIP(nn.Module):
         count, packing.text_layout) and returns the CLS rows."""
         text_args = (text,) if self.text_encode_without_mask else (text, text_mask)
         text_kwargs = None
-        if self._pack_text:
-            self._check_pack_text()                              # (dropout and train / eval mode are only known now)
+        if self._pack_text or self._pack_text_causal:
+            name = "pack_text" if self._pack_text else "pack_text_causal"
+            (self._check_pack_text if self._pack_text else self._check_pack_text_causal)()       # (dropout and train / eval mode are only known now)
             if not cls_row_only:
-                raise NotImplementedError("CLIP.pack_text is not available with return_encodings=True (the encoding of every row is returned)")
-            from .packing import text_layout
-            text_kwargs = dict(layout=layout if layout is not None else text_layout(text, self.text_pad_id, mask=text_mask))
+                raise NotImplementedError(f"CLIP.{name} is not available with return_encodings=True (the encoding of every row is returned)")
+            text_kwargs = dict(layout=layout if layout is not None else self._packed_layout(text, text_mask))
             if self.pack_text_pool_last:
-                text_kwargs["pool_row"] = 0
+                text_kwargs["pool_row"] = 0 if self._pack_text else "eos"
             return text_args, text_kwargs
         if layout is not None:
-            raise ValueError("text_layout was passed but CLIP.pack_text is off")
+            raise ValueError("text_layout was passed but CLIP.pack_text (or pack_text_causal) is off")
         if (cls_row_only and self.prune_unused_rows and isinstance(self.text_transformer, TextTransformer) and self.text_has_cls_token
                 and not self.text_causal_mask):
             text_kwargs = dict(pool_row=0)
@@ -557,7 +598,7 @@ class CLIP(nn.Module):
     def _join_text(self, enc_text_parts, text):
         """the slices of _encode_text as one encoding, the EOS row in front under a causal mask (x_clip.py:670-685, its `b` is the batch size)"""
         enc_text = enc_text_parts[0] if len(enc_text_parts) == 1 else torch.cat(enc_text_parts, dim=0)
-        if self.text_causal_mask:
+        if self.text_causal_mask and enc_text.ndim == 3:        # (the packed causal tower returns the EOS rows themselves, [b, dim])
             enc_text = XF.eos_to_front(enc_text, text, self.text_eos_id)
         return enc_text
 
@@ -720,7 +761,7 @@ class CLIP(nn.Module):
         aug_image=None,
         text_layout=None
     ):
-        """text_layout (not a reference keyword; needs `pack_text`): packing.text_layout(text, pad_id=text_pad_id) built ahead of time, e.g. from
+        """text_layout (not a reference keyword; needs `pack_text`, or `pack_text_causal` with has_cls=False, eos_id=text_eos_id): packing.text_layout(text, pad_id=text_pad_id) built ahead of time, e.g. from
         the loader's CPU tokens -- the step then reads nothing back from the device.  Augmented texts get their own layout here, through the same code."""
         batch, device = text.shape[0], text.device
 
@@ -742,8 +783,8 @@ class CLIP(nn.Module):
             aug_text = torch.cat(aug_text, dim=0)
             aug_text_mask = aug_text != self.text_pad_id
             if exists(text_layout):
-                from .packing import cat_layouts, text_layout as make_layout
-                text_layout = cat_layouts([text_layout, make_layout(aug_text, self.text_pad_id)])
+                from .packing import cat_layouts
+                text_layout = cat_layouts([text_layout, self._packed_layout(aug_text)])
             text_mask = torch.cat((text_mask, aug_text_mask), dim=0)
             text = torch.cat((text, aug_text), dim=0)
 

@@ -85,10 +85,23 @@ XC_DEV void a3_fwd_step(const unsigned char* Ks, const unsigned char* Vs, const 
     for (int kb = 0; kb < 4; ++kb) s = mma_kblock(a3_row_frag(Ks, t, kb, lane), qf[kb], s, (bf16_t*)nullptr);
     bool valid[16];
     float mx = ATT_NEG;
+    if (CAUSAL && !MASKED) {
+        // the causal rule alone (the packed kernels' diagonal sub-tile): a hidden score is REPLACED by ATT_NEG, whose probability below is
+        // exp2(ATT_NEG scale2 - m) = exactly 0 -- the value the select of the masked variant gives -- and no flag outlives this loop (sixteen
+        // lane masks held across the exponentials spilled this variant to scratch).  Every lane sees at least key t * 32 here: the caller
+        // only passes a sub-tile that starts at or below the lane's query.
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        valid[r] = (!MASKED || Ms[t * 32 + mfma_row(r, lane)] != 0) && (!CAUSAL || t * 32 + mfma_row(r, lane) <= qidx);
-        mx = fmaxf(mx, valid[r] ? s[r] : ATT_NEG);
+        for (int r = 0; r < 16; ++r) {
+            valid[r] = true;
+            s[r] = t * 32 + mfma_row(r, lane) <= qidx ? s[r] : ATT_NEG;
+            mx = fmaxf(mx, s[r]);
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            valid[r] = (!MASKED || Ms[t * 32 + mfma_row(r, lane)] != 0) && (!CAUSAL || t * 32 + mfma_row(r, lane) <= qidx);
+            mx = fmaxf(mx, valid[r] ? s[r] : ATT_NEG);
+        }
     }
     mx = fmaxf(mx, shfl_xor(mx, 32));
     const float m_new = fmaxf(m2, mx > 0.5f * ATT_NEG ? mx * scale2 : ATT_NEG);
@@ -97,7 +110,7 @@ XC_DEV void a3_fwd_step(const unsigned char* Ks, const unsigned char* Vs, const 
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         float pv = fast_exp2(s[r] * scale2 - m_new);
-        if (MASKED || CAUSAL) pv = valid[r] ? pv : 0.f;
+        if (MASKED) pv = valid[r] ? pv : 0.f;
         s[r] = pv;
         rs += pv;
     }
@@ -117,13 +130,19 @@ XC_DEV void a3_fwd_step(const unsigned char* Ks, const unsigned char* Vs, const 
 }
 // votes on the sub-tile's key validity and runs the matching variant; with CAUSAL the wave's queries are [qlo, qlo + 32): sub-tiles
 // entirely above the diagonal are skipped, the ones straddling it take the per-element comparison
-template <bool CAUSAL>
+// KEYMASK = false (only with CAUSAL, and only where the unit has no key mask: the packed kernels): Ms[k] = (k < n) then, and a query i < n that
+// sees key j <= i sees a key below n -- the diagonal sub-tile needs no validity bytes (a query lane at or past n is stored by nobody and reads
+// the finite clamped rows of the image), and a sub-tile below the diagonal of a block that holds a real query is all valid without a vote.
+// The probabilities are the same numbers either way.
+template <bool CAUSAL, bool KEYMASK = true>
 XC_DEV void a3_fwd_step_auto(const unsigned char* Ks, const unsigned char* Vs, const unsigned char* Ms, int t, const u32x4 (&qf)[4],
                              float scale2, int lane, int qlo, f32x16 (&o)[2], float& m2, float& l) {
+    static_assert(KEYMASK || CAUSAL, "only the causal rule makes the validity bytes redundant");
     const int qidx = qlo + (lane & 31);
     if (CAUSAL) {
         if (t * 32 > qlo + 31) return;
-        if (t * 32 + 31 > qlo) { a3_fwd_step<true, true>(Ks, Vs, Ms, t, qf, scale2, lane, qidx, o, m2, l); return; }
+        if (t * 32 + 31 > qlo) { a3_fwd_step<KEYMASK, true>(Ks, Vs, Ms, t, qf, scale2, lane, qidx, o, m2, l); return; }
+        if (!KEYMASK) { a3_fwd_step<false, false>(Ks, Vs, Ms, t, qf, scale2, lane, qidx, o, m2, l); return; }
     }
     const bool kv = Ms[t * 32 + (lane & 31)] != 0;
     if (wave_all(kv)) a3_fwd_step<false, false>(Ks, Vs, Ms, t, qf, scale2, lane, qidx, o, m2, l);
@@ -221,11 +240,22 @@ XC_DEV A3Unit a3_unit(const bf16_t* qkv, const bf16_t* o, const bf16_t* dout, bf
     return u;
 }
 
+// natural-log lse of a block's row from its running maximum (log2 units) and sum.  Under -ffp-contract=fast the compiler decided per
+// instantiation whether `m ln 2 + log l` became one fma: the non-causal kernels got the fma, the dense causal kernel a product rounded on its
+// own (1 ulp of fp32 apart).  The packed causal kernel shares that body and must give its bits, so the causal rounding is pinned here as what
+// it has been -- product, then sum -- instead of being left to the scheduler (the product passes through `opaque`: the back end fuses across
+// a contraction pragma under that flag); the non-causal expression is untouched.
+template <bool CAUSAL>
+XC_DEV float a3_block_lse(float m2, float l) {
+    if (CAUSAL) return u2f(opaque(__builtin_bit_cast(uint32_t, m2 * 0.6931471805599453f))) + logf(l);
+    return m2 * 0.6931471805599453f + logf(l);                 // m is in log2 units
+}
+
 // ---- forward ----------------------------------------------------------------------------------------------------------
 // RAGGED: the launch (waves, LDS) may be sized for a longer unit than this one (attention_varlen.h) -- wave w >= a3_waves(n) then owns no
 // query block; it still loads, takes its share of a cooperative tail and meets every barrier.  Nothing else differs, and with
 // RAGGED = false `own` is the constant true.
-template <bool CAUSAL, bool RAGGED>
+template <bool CAUSAL, bool RAGGED, bool KEYMASK = true>
 XC_DEV void a3_fwd_unit(const A3Unit& u, float scale) {
     XC_LDS_DYNAMIC(lds);
     const int n = u.n, npad = (n + 31) & ~31;
@@ -285,7 +315,12 @@ XC_DEV void a3_fwd_unit(const A3Unit& u, float scale) {
                 a3_tail_outer(Vs, tcoop, 0, 1.f, lane, o);
             }
         }
-        for (int t = wave; t < tcoop; t += nwaves) a3_fwd_step_auto<CAUSAL>(Ks, Vs, Ms, t, qf, scale2, lane, tail0, o, m, l);
+        if (CAUSAL && !KEYMASK) {                              // as below: the full sub-tiles lie under the tail's diagonal, the tail's own is the last
+            for (int t = wave; t < nsub - 1; t += nwaves) a3_fwd_step<false, false>(Ks, Vs, Ms, t, qf, scale2, lane, tail0 + c31, o, m, l);
+            if (tcoop == nsub && (nsub - 1) % nwaves == wave) a3_fwd_step<false, true>(Ks, Vs, Ms, nsub - 1, qf, scale2, lane, tail0 + c31, o, m, l);
+        } else {
+            for (int t = wave; t < tcoop; t += nwaves) a3_fwd_step_auto<CAUSAL, KEYMASK>(Ks, Vs, Ms, t, qf, scale2, lane, tail0, o, m, l);
+        }
         if (c31 < ntail) {
             float* rec = Ts + ((long)wave * A3_TAIL_MAX + c31) * A3_TAIL_REC;
             if (h == 0) { rec[0] = m; rec[1] = l; }
@@ -314,7 +349,13 @@ XC_DEV void a3_fwd_unit(const A3Unit& u, float scale) {
                 a3_tail_outer(Vs, tend, 0, 1.f, lane, o);
             }
         }
-        for (int t = 0; t < tend; ++t) a3_fwd_step_auto<CAUSAL>(Ks, Vs, Ms, t, qf, scale2, lane, q0, o, m, l);
+        if (CAUSAL && !KEYMASK) {                              // the sub-tiles below the block's diagonal one, then that one: one variant per loop
+            const int td = q0 >> 5;
+            for (int t = 0; t < td; ++t) a3_fwd_step<false, false>(Ks, Vs, Ms, t, qf, scale2, lane, qrow, o, m, l);
+            if (td < tend) a3_fwd_step<false, true>(Ks, Vs, Ms, td, qf, scale2, lane, qrow, o, m, l);
+        } else {
+            for (int t = 0; t < tend; ++t) a3_fwd_step_auto<CAUSAL, KEYMASK>(Ks, Vs, Ms, t, qf, scale2, lane, q0, o, m, l);
+        }
     }
     sync();                                                    // every wave is done with the K / V images (and the tail partials are in)
     // Store bound n: with a cooperative tail the waves that own a block are the n / 32 full ones, so their rows q0 .. q0 + 31 all lie
@@ -322,7 +363,7 @@ XC_DEV void a3_fwd_unit(const A3Unit& u, float scale) {
     if (own) {
         const float inv = l > 0.f ? 1.0f / l : 0.f;
         a2_store_rows(lds + wave * 32 * 144, o, inv, u.out, u.ldo, q0, n, lane);
-        if (h == 0 && qrow < n) u.lse[qrow] = m * 0.6931471805599453f + logf(l);    // m is in log2 units
+        if (h == 0 && qrow < n) u.lse[qrow] = a3_block_lse<CAUSAL>(m, l);
     }
     if (coop && wave == 0) {                                   // merge the nwaves partials of every tail row; lane = feature d
         // (the staging blocks of a2_store_rows lie in [0, nwaves 32 144) of the LDS, the partials behind both images: no overlap)

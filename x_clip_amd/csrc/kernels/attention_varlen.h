@@ -9,6 +9,9 @@
 //   dqkv [R, 3, heads, HS]   fully overwritten
 // Every key of a sample is visible to every query of that sample and to no other: no mask, no causal flag, no dropout.  A work-group (or
 // wave) only ever stores rows of the unit it owns, so nothing is written outside [0, R); no atomics, a fixed summation order.
+// The *_causal_* kernels are the same over the same arrays with ONE more rule (the autoregressive text encoder, x_clip.py:231-234): key row j
+// is visible to query row i of its sample iff j <= i, by PACKED row index -- kept rows keep their order, so that is the dense rule on the
+// rows that exist.  A row's lse is then over keys [cu[s], row], and a row sees at least itself.
 //
 // Two forms:
 //   * head-resident (bf16, HS = 64, max_len <= A3_MAX_N): wrappers around attention3.h's bodies a3_fwd_unit / a3_bwd_unit, which the dense
@@ -20,7 +23,8 @@
 //     the same out, lse and dQ bits, tests/pooled_packed_cases.py case_plain_varlen_equals_pool_varlen_bits).  The forward is a wrapper
 //     around ap_fwd_unit; the backward's wave takes its row first as a query (dQ: a copy of ap_bwd_unit's loop, see the kernel) and then as
 //     a key (dK, dV: the sample's queries stream past it -- another loop, three loads per row).  O(len) work per row, L2-resident
-//     re-reads: a correctness path, not a fast one.
+//     re-reads: a correctness path, not a fast one.  Causal: the forward's visible range ends at the row itself (ApUnit::kvis = r + 1), the
+//     backward's query half runs over keys [k0, r] and its key half over queries [r, k1).
 #pragma once
 #include "attention3.h"
 #include "attention_pool.h"
@@ -48,7 +52,8 @@ XC_DEV int av_sample_of(const int* cu, int batch, int r) {
 
 // the unit of wave blockIdx.x * 4 + wave_id(): row r of head h as the QUERY of its own sample's keys, all of them visible; false: the wave
 // is past the last unit and leaves whole (no barriers anywhere).  attention_pool.h's ApUnit with K / V in the same array as the query
-template <typename T, int HS>
+// (CAUSAL: the keys behind the row are hidden, kvis = r + 1)
+template <typename T, int HS, bool CAUSAL = false>
 XC_DEV bool av_plain_unit(const AttnVarlenParams& p, ApUnit<T>& u) {
     const long unit = (long)blockIdx.x * 4 + wave_id();
     if (unit >= (long)p.rows * p.heads) return false;
@@ -59,19 +64,20 @@ XC_DEV bool av_plain_unit(const AttnVarlenParams& p, ApUnit<T>& u) {
     const T* qkv = static_cast<const T*>(p.qkv) + (long)h * HS;
     T* dqkv = static_cast<T*>(p.dqkv) + (long)h * HS;
     u = {qkv + r * ldq, static_cast<const T*>(p.dout) + at, static_cast<T*>(p.out) + at, p.lse + (long)h * p.rows + r,
-         qkv + inner, ldq, inner, nullptr, k0, k1, k1, dqkv + r * ldq, dqkv + inner};
+         qkv + inner, ldq, inner, nullptr, k0, k1, CAUSAL ? r + 1 : k1, dqkv + r * ldq, dqkv + inner};
     return true;
 }
 
-template <typename T, int HS>
+template <typename T, int HS, bool CAUSAL = false>
 __global__ __launch_bounds__(256) void attn_varlen_plain_fwd_kernel(AttnVarlenParams p) {
     ApUnit<T> u;
-    if (av_plain_unit<T, HS>(p, u)) ap_fwd_unit<T, HS>(u, p.scale);
+    if (av_plain_unit<T, HS, CAUSAL>(p, u)) ap_fwd_unit<T, HS>(u, p.scale);
 }
 
 // The query half below is ap_bwd_unit's loop without the dK / dV stores, kept as its own copy: called through the body, the bf16 HS = 128
 // instantiation takes 82 registers instead of 80 and falls from 6 to 5 waves per SIMD (measured 5 % slower; profiles/r19_pool_one_loop_*).
-template <typename T, int HS>
+// CAUSAL only moves the two loops' bounds (constants of the instantiation): keys [k0, r] for the row as a query, queries [r, k1) for it as a key.
+template <typename T, int HS, bool CAUSAL = false>
 __global__ __launch_bounds__(256) void attn_varlen_plain_bwd_kernel(AttnVarlenParams p) {
     constexpr int VEC = Elem<T>::VEC, CH = HS / VEC, KPL = 64 / CH;
     const int lane = lane_id();
@@ -80,6 +86,8 @@ __global__ __launch_bounds__(256) void attn_varlen_plain_bwd_kernel(AttnVarlenPa
     const int r = (int)(unit / p.heads), h = (int)(unit % p.heads);
     const int s = av_sample_of(p.cu, p.batch, r);
     const int k0 = p.cu[s], k1 = p.cu[s + 1];
+    const int kend = CAUSAL ? r + 1 : k1;                      // the keys row r sees: [k0, kend)
+    const int q0 = CAUSAL ? r : k0;                            // the queries that see row r: [q0, k1)
     const int inner = p.heads * HS;
     const long ldq = 3L * inner;
     const int g = lane / CH, c = lane % CH;
@@ -102,9 +110,9 @@ __global__ __launch_bounds__(256) void attn_varlen_plain_bwd_kernel(AttnVarlenPa
     float dq[VEC];
 #pragma unroll
     for (int e = 0; e < VEC; ++e) dq[e] = 0.f;
-    for (int j0 = k0; j0 < k1; j0 += KPL) {
+    for (int j0 = k0; j0 < kend; j0 += KPL) {
         const int j = j0 + g;
-        const bool live = j < k1;
+        const bool live = j < kend;
         const int jr = live ? j : k1 - 1;
         float kf[VEC], vf[VEC];
         load_vec<T>(qkv + (long)jr * ldq + inner, kf);
@@ -129,7 +137,7 @@ __global__ __launch_bounds__(256) void attn_varlen_plain_bwd_kernel(AttnVarlenPa
     load_vec<T>(qkv + (long)r * ldq + 2 * inner, vv);
 #pragma unroll
     for (int e = 0; e < VEC; ++e) { dk[e] = 0.f; dv[e] = 0.f; }
-    for (int i0 = k0; i0 < k1; i0 += KPL) {
+    for (int i0 = q0; i0 < k1; i0 += KPL) {
         const int i = i0 + g;
         const bool live = i < k1;
         const int ir = live ? i : k1 - 1;
@@ -178,6 +186,15 @@ __global__ __launch_bounds__(576) XC_FOUR_WAVES_PER_SIMD void attn_varlen_fwd_ke
 __global__ __launch_bounds__(256) void attn_varlen_bwd_kernel(AttnVarlenParams p) {
     A3Unit u;
     if (av_unit(p, u)) a3_bwd_unit<false>(u, p.scale);
+}
+// the causal twins: the same unit, launch sizing and bounds; the bodies' CAUSAL skips the sub-tiles above the diagonal
+__global__ __launch_bounds__(576) XC_FOUR_WAVES_PER_SIMD void attn_varlen_causal_fwd_kernel(AttnVarlenParams p) {
+    A3Unit u;
+    if (av_unit(p, u)) a3_fwd_unit<true, true, false>(u, p.scale);      // (no key mask in a packed unit)
+}
+__global__ __launch_bounds__(256) void attn_varlen_causal_bwd_kernel(AttnVarlenParams p) {
+    A3Unit u;
+    if (av_unit(p, u)) a3_bwd_unit<true>(u, p.scale);
 }
 
 // launch sizes for a batch whose longest sample has max_len rows: every shorter unit fits the same carve.  The backward always carves the

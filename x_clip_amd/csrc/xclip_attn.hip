@@ -124,6 +124,10 @@ XC_WAVE_FAMILY(PoolKernels, AttnPoolParams, attn_pool_fwd_kernel, attn_pool_bwd_
 XC_WAVE_FAMILY(PoolVarlenKernels, AttnPoolVarlenParams, attn_pool_varlen_fwd_kernel, attn_pool_varlen_bwd_kernel);
 XC_WAVE_FAMILY(VarlenPlainKernels, AttnVarlenParams, attn_varlen_plain_fwd_kernel, attn_varlen_plain_bwd_kernel);
 #undef XC_WAVE_FAMILY
+template <typename T, int HS> struct VarlenPlainCausalKernels {   // (the same kernel templates, CAUSAL = true)
+    static constexpr void (*fwd)(AttnVarlenParams) = attn_varlen_plain_fwd_kernel<T, HS, true>;
+    static constexpr void (*bwd)(AttnVarlenParams) = attn_varlen_plain_bwd_kernel<T, HS, true>;
+};
 
 // ---- one query row per (sample, head) (kernels/attention_pool.h) ----
 // the common checks and fields of the dense pair; ptr_err: the entry point's own pointer complaint, or null; -> 0, or 1 with the error recorded
@@ -334,45 +338,85 @@ static inline bool attn_varlen_resident(int dtype, int64_t head_dim, int64_t max
     return dtype == XCLIP_BF16 && head_dim == 64 && max_len <= xc::A3_MAX_N;
 }
 
-extern "C" {
-
-int xclip_attention_varlen_fwd(const void* qkv, const int32_t* cu, void* out, float* lse, int64_t rows, int64_t batch, int64_t heads,
-                               int64_t head_dim, int64_t max_len, float scale, int dtype, void* stream) {
+// plain form: the family by the causal switch
+template <bool CAUSAL, typename T>
+static void launch_varlen_plain(const xc::AttnVarlenParams& p, int64_t units, int64_t head_dim, bool backward, hipStream_t st) {
+    if (CAUSAL) launch_wave_per_unit<VarlenPlainCausalKernels, T>(p, units, head_dim, backward, st);
+    else launch_wave_per_unit<VarlenPlainKernels, T>(p, units, head_dim, backward, st);
+}
+// both entry-point pairs: CAUSAL picks the kernels, everything else (checks, routing, launch sizes) is shared
+template <bool CAUSAL>
+static int attn_varlen_fwd(const char* fn, const void* qkv, const int32_t* cu, void* out, float* lse, int64_t rows, int64_t batch, int64_t heads,
+                           int64_t head_dim, int64_t max_len, float scale, int dtype, void* stream) {
     AttnVarlenParams p;
-    const int rc = attn_varlen_setup(__func__, qkv, cu, rows, batch, heads, head_dim, max_len, scale, dtype,
+    const int rc = attn_varlen_setup(fn, qkv, cu, rows, batch, heads, head_dim, max_len, scale, dtype,
                                      qkv && out && lse && aligned16(qkv) && aligned16(out), p);
     if (rc != 0 || batch == 0) return rc;
     p.out = out; p.lse = lse;
     hipStream_t st = (hipStream_t)stream;
     if (attn_varlen_resident(dtype, head_dim, max_len)) {
         const int lds = attn_varlen_fwd_lds_bytes((int)max_len);
-        XC_REQUIRE(lds <= 160 * 1024, "internal: varlen forward LDS");
-        XC_ALLOW_LDS(attn_varlen_fwd_kernel, 160 * 1024);
-        hipLaunchKernelGGL(attn_varlen_fwd_kernel, dim3((unsigned)(batch * heads)), dim3(attn_varlen_fwd_waves((int)max_len) * 64), lds, st, p);
+        if (lds > 160 * 1024) return xcapi::fail(fn, "internal: varlen forward LDS");
+        const dim3 grid((unsigned)(batch * heads)), block(attn_varlen_fwd_waves((int)max_len) * 64);
+        if (CAUSAL) {
+            XC_ALLOW_LDS(attn_varlen_causal_fwd_kernel, 160 * 1024);
+            hipLaunchKernelGGL(attn_varlen_causal_fwd_kernel, grid, block, lds, st, p);
+        } else {
+            XC_ALLOW_LDS(attn_varlen_fwd_kernel, 160 * 1024);
+            hipLaunchKernelGGL(attn_varlen_fwd_kernel, grid, block, lds, st, p);
+        }
     } else {
-        by_dtype(dtype, [&](auto t) { launch_wave_per_unit<VarlenPlainKernels, typename decltype(t)::type>(p, rows * heads, head_dim, false, st); });
+        by_dtype(dtype, [&](auto t) { launch_varlen_plain<CAUSAL, typename decltype(t)::type>(p, rows * heads, head_dim, false, st); });
     }
-    return check_launch(__func__);
+    return check_launch(fn);
 }
 
-int xclip_attention_varlen_bwd(const void* qkv, const int32_t* cu, const void* out, const void* dout, const float* lse, void* dqkv,
-                               int64_t rows, int64_t batch, int64_t heads, int64_t head_dim, int64_t max_len, float scale, int dtype,
-                               void* stream) {
+template <bool CAUSAL>
+static int attn_varlen_bwd(const char* fn, const void* qkv, const int32_t* cu, const void* out, const void* dout, const float* lse, void* dqkv,
+                           int64_t rows, int64_t batch, int64_t heads, int64_t head_dim, int64_t max_len, float scale, int dtype,
+                           void* stream) {
     AttnVarlenParams p;
-    const int rc = attn_varlen_setup(__func__, qkv, cu, rows, batch, heads, head_dim, max_len, scale, dtype,
+    const int rc = attn_varlen_setup(fn, qkv, cu, rows, batch, heads, head_dim, max_len, scale, dtype,
                                      qkv && out && dout && lse && dqkv && aligned16(qkv) && aligned16(out) && aligned16(dout) && aligned16(dqkv), p);
     if (rc != 0 || batch == 0) return rc;
     p.out = const_cast<void*>(out); p.lse = const_cast<float*>(lse); p.dout = dout; p.dqkv = dqkv;
     hipStream_t st = (hipStream_t)stream;
     if (attn_varlen_resident(dtype, head_dim, max_len)) {
         const int lds = attn_varlen_bwd_lds_bytes((int)max_len);
-        XC_REQUIRE(lds <= 160 * 1024, "internal: varlen backward LDS");
-        XC_ALLOW_LDS(attn_varlen_bwd_kernel, 160 * 1024);
-        hipLaunchKernelGGL(attn_varlen_bwd_kernel, dim3((unsigned)(batch * heads)), dim3(attn_varlen_bwd_waves((int)max_len) * 64), lds, st, p);
+        if (lds > 160 * 1024) return xcapi::fail(fn, "internal: varlen backward LDS");
+        const dim3 grid((unsigned)(batch * heads)), block(attn_varlen_bwd_waves((int)max_len) * 64);
+        if (CAUSAL) {
+            XC_ALLOW_LDS(attn_varlen_causal_bwd_kernel, 160 * 1024);
+            hipLaunchKernelGGL(attn_varlen_causal_bwd_kernel, grid, block, lds, st, p);
+        } else {
+            XC_ALLOW_LDS(attn_varlen_bwd_kernel, 160 * 1024);
+            hipLaunchKernelGGL(attn_varlen_bwd_kernel, grid, block, lds, st, p);
+        }
     } else {
-        by_dtype(dtype, [&](auto t) { launch_wave_per_unit<VarlenPlainKernels, typename decltype(t)::type>(p, rows * heads, head_dim, true, st); });
+        by_dtype(dtype, [&](auto t) { launch_varlen_plain<CAUSAL, typename decltype(t)::type>(p, rows * heads, head_dim, true, st); });
     }
-    return check_launch(__func__);
+    return check_launch(fn);
+}
+
+extern "C" {
+
+int xclip_attention_varlen_fwd(const void* qkv, const int32_t* cu, void* out, float* lse, int64_t rows, int64_t batch, int64_t heads,
+                               int64_t head_dim, int64_t max_len, float scale, int dtype, void* stream) {
+    return attn_varlen_fwd<false>(__func__, qkv, cu, out, lse, rows, batch, heads, head_dim, max_len, scale, dtype, stream);
+}
+int xclip_attention_varlen_bwd(const void* qkv, const int32_t* cu, const void* out, const void* dout, const float* lse, void* dqkv,
+                               int64_t rows, int64_t batch, int64_t heads, int64_t head_dim, int64_t max_len, float scale, int dtype,
+                               void* stream) {
+    return attn_varlen_bwd<false>(__func__, qkv, cu, out, dout, lse, dqkv, rows, batch, heads, head_dim, max_len, scale, dtype, stream);
+}
+int xclip_attention_varlen_causal_fwd(const void* qkv, const int32_t* cu, void* out, float* lse, int64_t rows, int64_t batch, int64_t heads,
+                                      int64_t head_dim, int64_t max_len, float scale, int dtype, void* stream) {
+    return attn_varlen_fwd<true>(__func__, qkv, cu, out, lse, rows, batch, heads, head_dim, max_len, scale, dtype, stream);
+}
+int xclip_attention_varlen_causal_bwd(const void* qkv, const int32_t* cu, const void* out, const void* dout, const float* lse, void* dqkv,
+                                      int64_t rows, int64_t batch, int64_t heads, int64_t head_dim, int64_t max_len, float scale, int dtype,
+                                      void* stream) {
+    return attn_varlen_bwd<true>(__func__, qkv, cu, out, dout, lse, dqkv, rows, batch, heads, head_dim, max_len, scale, dtype, stream);
 }
 
 }  // extern "C"

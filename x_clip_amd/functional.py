@@ -202,7 +202,8 @@ def _attn_forward(h: Tensor, W: LayerWeights, c: _Pass, seed: int):
     spec, inner = c.spec, c.spec.inner
     qkv = ops.gemm(h, W.w_qkv, M, 3 * inner, D)                                        # to_qkv            :216
     if c.layout is not None:                                   # samples of different lengths, end to end: no mask, no rotary, no dropout (text_encode_packed)
-        o, lse = ops.attention_varlen_fwd(qkv, c.layout.cu, c.layout.max_len, spec.heads, spec.scale, spec.head_slot)
+        fwd = ops.attention_varlen_causal_fwd if spec.causal else ops.attention_varlen_fwd      # (causal: key j <= query i by packed row)
+        o, lse = fwd(qkv, c.layout.cu, c.layout.max_len, spec.heads, spec.scale, spec.head_slot)
         return qkv, o, lse
     if spec.rotary is not None:
         ops.rotary_(qkv, c.n, spec.rotary, head_dim=spec.head_slot)                    # q, k, v rotated   :221-223
@@ -260,7 +261,8 @@ def _attn_backward(do: Tensor, t: LayerTape, c: _Pass, seed: int) -> Tensor:
     """the dense attention: gradient w.r.t. its output [M, inner] -> gradient w.r.t. the packed rotated qkv [M, 3 inner]"""
     spec, B, n, inner = c.spec, c.B, c.n, c.spec.inner
     if c.layout is not None:
-        return ops.attention_varlen_bwd(t.qkv, c.layout.cu, c.layout.max_len, t.o, do, t.lse, spec.heads, spec.scale, spec.head_slot)
+        bwd = ops.attention_varlen_causal_bwd if spec.causal else ops.attention_varlen_bwd
+        return bwd(t.qkv, c.layout.cu, c.layout.max_len, t.o, do, t.lse, spec.heads, spec.scale, spec.head_slot)
     dqkv = ops.attention_bwd(t.qkv.view(B, n, 3 * inner), c.mask, t.o, do.view(B, n, inner), t.lse, spec.heads, spec.scale, spec.causal, spec.head_slot, spec.attn_dropout, seed)
     return dqkv.view(B * n, 3 * inner)
 
@@ -380,12 +382,20 @@ def _layer_backward_pooled(dx2: Tensor, t: LayerTape, W: LayerWeights, need: Lay
 
 
 # ---- the same for a packed batch (c.layout): the pooled row is the FIRST row of every sample, row cu[s] of the [R, D] arrays ----------------
+# -- or, for a layout that ends every sample at its first EOS token (the causal encoder, layout.ends_at_eos), its LAST row cu[s+1] - 1.  Under the
+# causal mask that row sees every row of its sample, which is what the one-query varlen attention computes: the kernels are the same, only
+# the rows the query / skip connection are gathered from (and their gradients added to) differ.
+def pooled_rows(layout) -> Tensor:
+    """int32 [batch]: the packed row the text head reads of every sample"""
+    return layout.cu[1:] - 1 if layout.ends_at_eos else layout.cu[:-1]
+
+
 # The rows of a sample are not a fixed stride apart, so the strided views above become gathers (xclip_gather_rows by cu[:-1]) and the two
 # "add into the pooled rows" become xclip_rows_add_at; the one-query attention reads each sample's own keys through cu
 # (attention_pool.h, the packed wrappers).  Same algebra and the same rounding points as the dense pooled layer above.
 def _layer_forward_pooled_packed(x: Tensor, W: LayerWeights, c: _Pass):
     spec, lay, inner = c.spec, c.layout, c.spec.inner
-    (R, D), B, first = x.shape, c.layout.batch, c.layout.cu[:-1]
+    (R, D), B, first = x.shape, c.layout.batch, pooled_rows(c.layout)
     h, m1, r1 = ops.layernorm_fwd(x, W.g_attn)                                         # PreNorm, every kept row   :126
     xc = ops.gather_rows(x, first)                                                     # the skip connection's pooled rows
     hc = ops.gather_rows(h, first)
@@ -400,7 +410,7 @@ def _layer_forward_pooled_packed(x: Tensor, W: LayerWeights, c: _Pass):
 def _layer_backward_pooled_packed(dx2: Tensor, t: LayerTape, W: LayerWeights, need: LayerWeights, dg: LayerWeights, c: _Pass, sg: _SideGemm):
     """dx2 [B, D]: gradient w.r.t. the CLS rows of the layer output -> (gradient w.r.t. the layer input [R, D], weight gradients)"""
     spec, lay, inner = c.spec, c.layout, c.spec.inner
-    (R, D), B, first = t.x.shape, c.layout.batch, c.layout.cu[:-1]
+    (R, D), B, first = t.x.shape, c.layout.batch, pooled_rows(c.layout)
     dx1, dp, d_ff1, d_ff2 = _ffn_backward(dx2, t, W, need, dg, c, sg, 0)
     q, kv, hc = t.qkv
     d_out = sg.wgrad(dp, t.o, D, inner, B, W.w_out) if need.w_out else None
@@ -436,6 +446,7 @@ def stack_forward(x0: Tensor, B: int, n: int, spec: StackSpec, params: Sequence[
     assert len(params) == 2 + LAYER_PARAMS * spec.depth
     assert pool_row is None or (can_pool(spec) and out is None and 0 <= pool_row < n)
     assert layout is None or (pool_row in (None, 0) and mask is None and out is None and x0.shape[0] == layout.R)
+    assert layout is None or spec.causal == layout.ends_at_eos, "a causal stack takes a layout that ends at the EOS row, and only it"
     x, m_in, r_in = ops.layernorm_fwd(x0, params[0])
     # dropout: one 64-bit seed per pass from torch's CPU generator (no device sync; torch.manual_seed makes it reproducible); layer l
     # uses seed + 2 l (attention) and seed + 2 l + 1 (feed-forward); the backward and a checkpointed re-run regenerate the same masks
@@ -619,7 +630,7 @@ class _PackedTextEncodeFn(torch.autograd.Function):
         ctx.save_for_backward(*stack)
         ctx.spec, ctx.layout, ctx.tape, ctx.pool_last = spec, layout, tape, pool_last
         ctx.meta = (E.shape[0], E.shape[1], 0 if P is None else P.shape[0], E.dtype)
-        return y if pool_last else ops.gather_rows(y, layout.cu[:-1])                    # enc_text[:, 0]                  :708
+        return y if pool_last else ops.gather_rows(y, pooled_rows(layout))               # enc_text[:, 0] (causal: of eos_to_front)  :708
 
     @staticmethod
     @once_differentiable
@@ -631,16 +642,16 @@ class _PackedTextEncodeFn(torch.autograd.Function):
         if not ctx.pool_last:
             # dy into the CLS rows of a zeroed [R, D]: as a gather, row r takes dy[s] where r = cu[s] and the appended zero row elsewhere
             src = torch.full((lay.R,), lay.batch, dtype=torch.int32, device=dyr.device)
-            src[lay.cu[:-1].long()] = torch.arange(lay.batch, dtype=torch.int32, device=dyr.device)
+            src[pooled_rows(lay).long()] = torch.arange(lay.batch, dtype=torch.int32, device=dyr.device)
             dyr = ops.gather_rows(torch.cat([dyr, dyr.new_zeros(1, D)], dim=0), src)
         dx0, sgrads = stack_backward(dyr, _take_tape(ctx), lay.batch, lay.max_len, ctx.spec, ctx.saved_tensors, None, need[3:], layout=lay)
         dE = dP = dcls = None
         if need[0] or need[1] or need[2]:
             tok_key, pos_key = lay.keys(vocab, npos)
-            aE, aP, acls = ops.text_embed_packed_bwd(dx0, tok_key, pos_key, lay.cu, vocab, npos, True, need_E=need[0], need_P=need[1])
+            aE, aP, acls = ops.text_embed_packed_bwd(dx0, tok_key, pos_key, lay.cu, vocab, npos, lay.has_cls, need_E=need[0], need_P=need[1])
             dE = ops.cast_from_f32(aE, dtype) if need[0] else None
             dP = ops.cast_from_f32(aP, dtype) if (need[1] and aP is not None) else None
-            dcls = ops.cast_from_f32(acls, dtype) if need[2] else None
+            dcls = ops.cast_from_f32(acls, dtype) if (need[2] and acls is not None) else None
         return (None, None, None, None, dE, dP, dcls, *sgrads)
 
 
@@ -650,12 +661,16 @@ def text_encode_packed(layout, E: Tensor, P: Optional[Tensor], cls: Optional[Ten
     the same tokens as text_encode(..., mask, pool_row=0), computed on the kept rows only.  Every layer runs on all R rows; with pool_last the
     last one runs its attention as one query per (sample, head) and everything behind it on the b CLS rows (the packed twin of the dense
     path's pooled last layer, with its rounding points: see _layer_forward_pooled)."""
-    if cls is None:
+    # the causal encoder: no CLS row, a causal mask, read at the first EOS token -- on a layout that ends every sample there (text_layout(eos_id=))
+    eos = cls is None and spec.causal and layout.ends_at_eos and not layout.has_cls
+    if cls is None and not eos:
         raise NotImplementedError("pack_text: the packed text tower returns the CLS row (text_has_cls_token=True)")
-    if spec.rotary is not None or spec.causal or spec.attn_dropout > 0.0 or spec.ff_dropout > 0.0:
+    if spec.rotary is not None or (spec.causal and not eos) or spec.attn_dropout > 0.0 or spec.ff_dropout > 0.0:
         raise NotImplementedError("pack_text: no rotary embedding (text_rotary_pos_emb), causal mask (text_causal_mask) or dropout in the packed text tower")
-    if not layout.has_cls or layout.R < layout.batch:
+    if not eos and (not layout.has_cls or layout.ends_at_eos or layout.R < layout.batch):
         raise ValueError("pack_text: the layout must keep a CLS row per sample (text_layout(..., has_cls=True))")
+    if eos and layout.R < layout.batch:
+        raise ValueError("pack_text_causal: the layout must keep every sample's EOS row")
     if P is not None and layout.n > P.shape[0]:
         raise IndexError(f"text length {layout.n} exceeds max_seq_len {P.shape[0]}")
     if layout.cu.device != E.device:

@@ -737,9 +737,7 @@ def attention_bwd(qkv: Tensor, mask: Optional[Tensor], out: Tensor, dout: Tensor
     return dqkv
 
 
-def attention_varlen_fwd(qkv: Tensor, cu: Tensor, max_len: int, heads: int, scale: float, head_dim: int = 64) -> Tuple[Tensor, Tensor]:
-    """samples of different lengths laid end to end: qkv [R, 3*heads*head_dim], cu int32 [b + 1] (sample s = rows cu[s] .. cu[s+1], each
-    1 .. max_len long); every key of a sample visible to every query of that sample and to no other -> out [R, heads*head_dim], lse fp32 [heads, R]"""
+def _attention_varlen_fwd(qkv: Tensor, cu: Tensor, max_len: int, heads: int, scale: float, head_dim: int, causal: bool) -> Tuple[Tensor, Tensor]:
     _dev_check(qkv, cu)
     qkv = _c(qkv)
     R, w = qkv.shape
@@ -747,32 +745,58 @@ def attention_varlen_fwd(qkv: Tensor, cu: Tensor, max_len: int, heads: int, scal
     assert cu.dtype == torch.int32 and cu.dim() == 1 and cu.is_contiguous() and cu.numel() >= 1
     out = torch.empty(R, heads * head_dim, dtype=qkv.dtype, device=qkv.device)
     lse = torch.empty(heads, R, dtype=torch.float32, device=qkv.device)
+    name = "xclip_attention_varlen_causal_fwd" if causal else "xclip_attention_varlen_fwd"
     probe = _probe(qkv)
     ev0 = probe.begin(qkv) if probe is not None else None
-    _lib.check(_lib.lib().xclip_attention_varlen_fwd(qkv.data_ptr(), cu.data_ptr(), out.data_ptr(), lse.data_ptr(), R, cu.numel() - 1, heads, head_dim,
-                                                     int(max_len), scale, dtype_code(qkv), _stream(qkv)), "xclip_attention_varlen_fwd")
+    _lib.check(getattr(_lib.lib(), name)(qkv.data_ptr(), cu.data_ptr(), out.data_ptr(), lse.data_ptr(), R, cu.numel() - 1, heads, head_dim,
+                                         int(max_len), scale, dtype_code(qkv), _stream(qkv)), name)
     if probe is not None:      # (the flop count needs the lengths, which live on the device: bytes only -- q, k, v in, o out)
-        probe.end(qkv, ev0, "attention", 0.0, 4 * R * heads * head_dim * qkv.element_size() + 4 * heads * R, "attn_varlen_fwd")
+        probe.end(qkv, ev0, "attention", 0.0, 4 * R * heads * head_dim * qkv.element_size() + 4 * heads * R,
+                  "attn_varlen_causal_fwd" if causal else "attn_varlen_fwd")
     return out, lse
 
 
-def attention_varlen_bwd(qkv: Tensor, cu: Tensor, max_len: int, out: Tensor, dout: Tensor, lse: Tensor, heads: int, scale: float,
-                         head_dim: int = 64) -> Tensor:
-    """-> dqkv [R, 3*heads*head_dim], every row written"""
+def _attention_varlen_bwd(qkv: Tensor, cu: Tensor, max_len: int, out: Tensor, dout: Tensor, lse: Tensor, heads: int, scale: float,
+                          head_dim: int, causal: bool) -> Tensor:
     _dev_check(qkv, cu, out, dout, lse)
     qkv, out, dout = _c(qkv), _c(out), _c(dout)
     R = qkv.shape[0]
     assert tuple(out.shape) == (R, heads * head_dim) and out.shape == dout.shape and dout.dtype == qkv.dtype
     assert lse.dtype == torch.float32 and lse.is_contiguous() and tuple(lse.shape) == (heads, R) and cu.dtype == torch.int32 and cu.is_contiguous()
     dqkv = torch.empty_like(qkv)
+    name = "xclip_attention_varlen_causal_bwd" if causal else "xclip_attention_varlen_bwd"
     probe = _probe(qkv)
     ev0 = probe.begin(qkv) if probe is not None else None
-    _lib.check(_lib.lib().xclip_attention_varlen_bwd(qkv.data_ptr(), cu.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), dqkv.data_ptr(), R,
-                                                     cu.numel() - 1, heads, head_dim, int(max_len), scale, dtype_code(qkv), _stream(qkv)),
-               "xclip_attention_varlen_bwd")
+    _lib.check(getattr(_lib.lib(), name)(qkv.data_ptr(), cu.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), dqkv.data_ptr(), R,
+                                         cu.numel() - 1, heads, head_dim, int(max_len), scale, dtype_code(qkv), _stream(qkv)), name)
     if probe is not None:      # q, k, v, o, dO in, dq, dk, dv out
-        probe.end(qkv, ev0, "attention", 0.0, 8 * R * heads * head_dim * qkv.element_size() + 8 * heads * R, "attn_varlen_bwd")
+        probe.end(qkv, ev0, "attention", 0.0, 8 * R * heads * head_dim * qkv.element_size() + 8 * heads * R,
+                  "attn_varlen_causal_bwd" if causal else "attn_varlen_bwd")
     return dqkv
+
+
+def attention_varlen_fwd(qkv: Tensor, cu: Tensor, max_len: int, heads: int, scale: float, head_dim: int = 64) -> Tuple[Tensor, Tensor]:
+    """samples of different lengths laid end to end: qkv [R, 3*heads*head_dim], cu int32 [b + 1] (sample s = rows cu[s] .. cu[s+1], each
+    1 .. max_len long); every key of a sample visible to every query of that sample and to no other -> out [R, heads*head_dim], lse fp32 [heads, R]"""
+    return _attention_varlen_fwd(qkv, cu, max_len, heads, scale, head_dim, False)
+
+
+def attention_varlen_bwd(qkv: Tensor, cu: Tensor, max_len: int, out: Tensor, dout: Tensor, lse: Tensor, heads: int, scale: float,
+                         head_dim: int = 64) -> Tensor:
+    """-> dqkv [R, 3*heads*head_dim], every row written"""
+    return _attention_varlen_bwd(qkv, cu, max_len, out, dout, lse, heads, scale, head_dim, False)
+
+
+def attention_varlen_causal_fwd(qkv: Tensor, cu: Tensor, max_len: int, heads: int, scale: float, head_dim: int = 64) -> Tuple[Tensor, Tensor]:
+    """attention_varlen_fwd under a causal mask: key row j of a sample is visible to its query row i iff j <= i (packed row order); a row's lse
+    is over the keys [cu[s], row]"""
+    return _attention_varlen_fwd(qkv, cu, max_len, heads, scale, head_dim, True)
+
+
+def attention_varlen_causal_bwd(qkv: Tensor, cu: Tensor, max_len: int, out: Tensor, dout: Tensor, lse: Tensor, heads: int, scale: float,
+                                head_dim: int = 64) -> Tensor:
+    """-> dqkv [R, 3*heads*head_dim] of attention_varlen_causal_fwd, every row written"""
+    return _attention_varlen_bwd(qkv, cu, max_len, out, dout, lse, heads, scale, head_dim, True)
 
 
 def attention_pool_fwd(q: Tensor, kv: Tensor, mask: Optional[Tensor], heads: int, scale: float, head_dim: int = 64,

@@ -8,6 +8,10 @@ its output: it can influence nothing and its gradient is exactly zero.  `text_la
     layout = text_layout(tokens, pad_id=0)            # tokens on the CPU (a loader's pinned buffer): no device read
     loss = clip(text, image, return_loss=True, text_layout=layout)
 
+The causal encoder (`CLIP.pack_text_causal`: no CLS row, a causal mask, read at the first EOS token) takes `text_layout(tokens, pad_id,
+has_cls=False, eos_id=...)`: under the causal mask a row behind the first EOS is a key of no row that is read either, so the layout ends every
+sample at that token and the pooled row is the sample's last, cu[s+1] - 1 (`TextLayout.ends_at_eos`).
+
 Built from CPU tokens the layout costs no device synchronisation: `R` and `max_len` are counted on the host and the index tensors are copied
 to the device asynchronously by `.to(device)`.  Built from DEVICE tokens -- the implicit path when `pack_text` is on and no layout is passed --
 it reads `R` and `max_len` back ONCE per call (one small device-to-host copy, the same kind of read the ragged multi-rank gather of
@@ -33,12 +37,13 @@ class TextLayout:
     batch: int
     n: int              # tokens per sample of the padded batch this was built from
     has_cls: bool
+    ends_at_eos: bool = False    # every sample's kept rows end at its first EOS token: the pooled row of sample s is cu[s+1] - 1
 
     def to(self, device, non_blocking: bool = True) -> "TextLayout":
         if self.cu.device == torch.device(device):
             return self
         mv = lambda t: (t.pin_memory() if (t.device.type == "cpu" and torch.device(device).type == "cuda") else t).to(device, non_blocking=non_blocking)
-        return TextLayout(mv(self.cu), mv(self.pos), mv(self.tok), self.R, self.max_len, self.batch, self.n, self.has_cls)
+        return TextLayout(mv(self.cu), mv(self.pos), mv(self.tok), self.R, self.max_len, self.batch, self.n, self.has_cls, self.ends_at_eos)
 
     def keys(self, vocab: int, npos: int):
         """(token key, position key) int64 [R] of the embedding gradient's segmented sums: the row's id / table position, and an id one past the
@@ -56,28 +61,42 @@ def cat_layouts(layouts) -> TextLayout:
     first = layouts[0]
     if len(layouts) == 1:
         return first
-    if any(l.n != first.n or l.has_cls != first.has_cls for l in layouts):
-        raise ValueError("cat_layouts: layouts of batches with the same sequence length and CLS convention")
+    if any(l.n != first.n or l.has_cls != first.has_cls or l.ends_at_eos != first.ends_at_eos for l in layouts):
+        raise ValueError("cat_layouts: layouts of batches with the same sequence length, CLS convention and ends_at_eos")
     layouts = [l.to(first.cu.device) for l in layouts]
     cus, off = [first.cu], first.R
     for l in layouts[1:]:
         cus.append(l.cu[1:] + off)
         off += l.R
     return TextLayout(torch.cat(cus), torch.cat([l.pos for l in layouts]), torch.cat([l.tok for l in layouts]), off,
-                      max(l.max_len for l in layouts), sum(l.batch for l in layouts), first.n, first.has_cls)
+                      max(l.max_len for l in layouts), sum(l.batch for l in layouts), first.n, first.has_cls, first.ends_at_eos)
 
 
-def text_layout(tokens: Tensor, pad_id: int = 0, mask: Optional[Tensor] = None, has_cls: bool = True) -> TextLayout:
+def text_layout(tokens: Tensor, pad_id: int = 0, mask: Optional[Tensor] = None, has_cls: bool = True, eos_id: Optional[int] = None) -> TextLayout:
     """tokens int64 [B, n] (+ an explicit bool key mask [B, n] instead of `tokens != pad_id`) -> the packed layout.  The CLS row of every sample
     is always kept (`F.pad(mask, (1, 0), True)`, x_clip.py:334); a pad id in mid-sequence is simply a dropped row -- exactly what the dense
-    masked attention computes.  The tensors live where `tokens` lives."""
+    masked attention computes.  The tensors live where `tokens` lives.
+
+    `eos_id` (the causal encoder, which has no CLS row and is read at its first EOS token, `eos_to_front` x_clip.py:675): a row is kept iff
+    the mask keeps it AND it lies at or before the sample's FIRST `eos_id` token.  Under the causal mask a row behind that token is a key of
+    no row that is read, so it is as dead as a padded one; and every sample's rows now END at its EOS (`ends_at_eos`), so the pooled row is
+    cu[s+1] - 1.  ValueError for a sample without the token (the assertion of `functional.eos_to_front`) or whose mask hides its first one."""
     if tokens.dim() != 2 or tokens.dtype != torch.int64:
         raise TypeError("text_layout: int64 tokens [batch, n]")
     B, n = tokens.shape
     keep = (tokens != pad_id) if mask is None else mask.to(torch.bool)
     if tuple(keep.shape) != (B, n):
         raise ValueError(f"text_layout: mask {tuple(keep.shape)} does not match tokens {(B, n)}")
-    if has_cls:
+    eos_ok = None
+    if eos_id is not None:
+        if has_cls:
+            raise ValueError("text_layout: eos_id describes the causal encoder, which has no CLS row (has_cls=False)")
+        is_eos = tokens == eos_id
+        upto = is_eos.to(torch.int32).cumsum(dim=1)
+        first = is_eos & (upto == 1)                            # the first EOS of each sample
+        keep = keep & ((upto == 0) | first)
+        eos_ok = (first & keep).any(dim=1).all() if B > 0 else None     # every sample has a first EOS and the mask keeps it
+    elif has_cls:
         keep = torch.cat([keep.new_ones(B, 1), keep], dim=1)
         tokens = torch.cat([tokens.new_zeros(B, 1), tokens], dim=1)
     elif B > 0 and not bool(keep.any(dim=1).all()):
@@ -87,8 +106,13 @@ def text_layout(tokens: Tensor, pad_id: int = 0, mask: Optional[Tensor] = None, 
     torch.cumsum(lens, 0, out=cu[1:])
     if B == 0:
         R = max_len = 0
-    else:
+    elif eos_ok is None:
         R, max_len = (int(v) for v in torch.stack([cu[-1], lens.max()]).tolist())      # (device tokens: the one read of this call)
+    else:                                                       # (the EOS check rides in the same read)
+        R, max_len, ok = (int(v) for v in torch.stack([cu[-1], lens.max(), eos_ok.to(torch.int32)]).tolist())
+        if not ok:
+            raise ValueError(f"text_layout: every sample needs an eos_id ({eos_id}) token that the mask keeps "
+                             "(a sample has none, or its first one is masked / a pad)")
     # kept (sample, position) pairs in row order.  On a device `nonzero` would read its result's size back (a second synchronisation):
     # a stable sort that moves the kept entries to the front, cut at the R already known
     if tokens.device.type == "cpu":
@@ -98,4 +122,4 @@ def text_layout(tokens: Tensor, pad_id: int = 0, mask: Optional[Tensor] = None, 
     npos = keep.shape[1]
     pos = (flat % npos).to(torch.int32)
     tok = tokens.reshape(-1)[flat].contiguous()
-    return TextLayout(cu.contiguous(), pos.contiguous(), tok, R, max_len, B, n, bool(has_cls))
+    return TextLayout(cu.contiguous(), pos.contiguous(), tok, R, max_len, B, n, bool(has_cls), eos_id is not None)
