@@ -20,7 +20,7 @@ extern "C" {
 #endif
 
 enum { XCLIP_F32 = 0, XCLIP_BF16 = 1 };
-#define XCLIP_ABI_VERSION 33
+#define XCLIP_ABI_VERSION 34
 
 int xclip_abi_version(void);
 const char* xclip_last_error(void);
@@ -434,6 +434,13 @@ int xclip_dwconv4s2_bwd(const void* dy, const void* x, const void* w, void* dx, 
  * inverse != 0 applies the transposed rotation = the backward of the forward call. */
 int xclip_rotary(void* x, int64_t ld, int64_t rows, int64_t n, int64_t slots, int64_t slot_width, int64_t rot, const float* inv_freq, int inverse,
                  int dtype, void* stream);
+/* The same rotation (RotaryEmbedding / apply_rotary_pos_emb, x_clip.py:155-176; applied to q, k and v, :221-223; rot: x_clip.py:311) for rows
+ * that carry their own position: token position of row r = pos[r] (device int32, `rows` entries) instead of r % n -- the packed text tower,
+ * whose kept rows lie end to end (pos = the row's position in its padded sample, 0 = the CLS row).  Everything else as xclip_rotary, and
+ * where pos[r] == r % n the same bits; ld may exceed slots * slot_width (the [R, 2 inner] keys | values of the pooled layer: slots =
+ * 2 * heads).  rows == 0: nothing is launched. */
+int xclip_rotary_pos(void* x, int64_t ld, int64_t rows, const int32_t* pos, int64_t slots, int64_t slot_width, int64_t rot, const float* inv_freq,
+                     int inverse, int dtype, void* stream);
 /* Similarity regularisation (x_clip.py:773-784): D[r,c] = A[r,c] - C[r,c] for two materialised similarity blocks (text-text and
  * image-image, [rows, cols] in the model dtype, row strides lda / ldc), 0 where c == r + diag_off (the global diagonal);
  * *sumsq_accum += sum D^2 (fp32, of the unrounded differences).  D (row stride ldd, model dtype) is the gradient factor:

@@ -78,6 +78,7 @@ _SIGNATURES = {
     "xclip_rowgrad": (c_int, [P, L, P, L, L, L, I, F, P, P, L, P, P]),
     "xclip_simreg_diff": (c_int, [P, L, P, L, P, L, L, L, L, P, I, P]),
     "xclip_rotary": (c_int, [P, L, L, L, L, L, L, P, I, I, P]),
+    "xclip_rotary_pos": (c_int, [P, L, L, P, L, L, L, P, I, I, P]),
     "xclip_layernorm_chain_fwd": (c_int, [P, P, P, P, P, P, P, P, P, P, L, L, F, I, P]),
     "xclip_layernorm_chain_bwd_workspace_bytes": (c_int64, [L, L]),
     "xclip_layernorm_chain_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, L, L, L, I, P]),
@@ -117,7 +118,7 @@ _SIGNATURES = {
     "xclip_grad_accumulate": (c_int, [P, L, L, I, P, I, P]),
 }
 EXPORTS = tuple(_SIGNATURES)
-ABI_VERSION = 33
+ABI_VERSION = 34
 
 
 def _bind(path: str):

@@ -211,7 +211,7 @@ class TextTransformer(nn.Module):
     def forward(self, x, mask=None, *, pool_row: Optional[int] = None, layout=None):
         """pool_row = r (not a reference keyword): the caller will read row r of every sample's encoding and nothing else -- the result is
         then [b, dim], and the last layer's row-wise part (to_out, feed-forward, norm_out) runs on those rows alone (functional.stack_forward).
-        layout (packing.TextLayout of x under its key mask; CLIP.pack_text): the tower runs on the kept rows only and returns the CLS rows [b, dim];
+        layout (packing.TextLayout of x under its key mask; CLIP.pack_text, or CLIP.pack_text_rotary for a rotary encoder): the tower runs on the kept rows only and returns the CLS rows [b, dim];
         with pool_row = 0 its last layer is the pooled one as well (CLIP.pack_text_pool_last).
         A causal encoder (CLIP.pack_text_causal) takes a layout that ends every sample at its first EOS token (text_layout(eos_id=)) and returns
         the EOS rows [b, dim] -- what `eos_to_front(...)[:, 0]` reads of the dense encoding; its pooled last layer is asked for with
@@ -465,6 +465,10 @@ class CLIP(nn.Module):
         # token that the key mask keeps.  A row behind it is a key of no row that is read, so it is as dead as a padded one; the pooled row is
         # the last kept row of the sample.  Off: every launch as before (pack_text itself goes on refusing a causal model)
         self._pack_text_causal = False
+        # opt-in, the same for the rotary encoder (text_rotary_pos_emb): q, k and v of a kept row are rotated by the position the row had in its
+        # padded sample (TextLayout.pos, xclip_rotary_pos) instead of by its dense row index.  Off: every launch as before (pack_text itself goes
+        # on refusing a rotary model)
+        self._pack_text_rotary = False
         # >1: the text batch runs through the text tower in that many slices, each on its own HIP stream.  The tower alternates
         # MFMA-bound GEMMs with HBM-bound row kernels; with two slices in flight one slice's LayerNorm / GEGLU kernels (no LDS, few
         # registers: they fit on a CU beside a persistent GEMM work-group) run under the other slice's GEMMs.  Encoders are row
@@ -512,6 +516,7 @@ class CLIP(nn.Module):
     @pack_text.setter
     def pack_text(self, on):
         if on:
+            self._one_packing("pack_text")
             self._check_pack_text()
         self._pack_text = bool(on)
 
@@ -545,6 +550,7 @@ class CLIP(nn.Module):
     @pack_text_causal.setter
     def pack_text_causal(self, on):
         if on:
+            self._one_packing("pack_text_causal")
             self._check_pack_text_causal()
         self._pack_text_causal = bool(on)
 
@@ -561,6 +567,44 @@ class CLIP(nn.Module):
             why = "attn_dropout / ff_dropout in the text tower (the keep-masks are indexed by dense position)"
         if why is not None:
             raise NotImplementedError(f"CLIP.pack_text_causal is not available with {why}")
+
+    @property
+    def pack_text_rotary(self) -> bool:
+        return self._pack_text_rotary
+
+    @pack_text_rotary.setter
+    def pack_text_rotary(self, on):
+        if on:
+            self._one_packing("pack_text_rotary")
+            self._check_pack_text_rotary()
+        self._pack_text_rotary = bool(on)
+
+    def _check_pack_text_rotary(self):
+        """pack_text_rotary is pack_text for the rotary CLS encoder alone: any other model is pointed at pack_text / pack_text_causal, and what
+        reads every row is out (the message names the option)"""
+        tt = self.text_transformer
+        if not isinstance(tt, TextTransformer) or not exists(tt.rotary_pos_emb):
+            raise ValueError("CLIP.pack_text_rotary packs the built-in rotary text encoder (text_rotary_pos_emb=True); for a CLS-token encoder "
+                             "with absolute positions set CLIP.pack_text, for the causal encoder CLIP.pack_text_causal")
+        why = None                                              # (text_causal_mask: refused with a rotary encoder at construction)
+        if self.use_all_token_embeds:
+            why = "use_all_token_embeds (the fine-grained head reads every token row)"
+        elif self.use_mlm:
+            why = "use_mlm (the masked-language-model head reads every token row)"
+        elif not self.text_has_cls_token or not exists(tt.cls_token):
+            why = "text_has_cls_token=False (the packed tower returns the CLS row)"
+        elif self.text_encode_without_mask:
+            why = "text_encode_without_mask (without a key mask the padded rows are attended to: nothing can be dropped)"
+        elif tt.transformer.training and (tt.transformer.attn_dropout > 0. or tt.transformer.ff_dropout > 0.):
+            why = "attn_dropout / ff_dropout in the text tower (the keep-masks are indexed by dense position)"
+        if why is not None:
+            raise NotImplementedError(f"CLIP.pack_text_rotary is not available with {why}")
+
+    def _one_packing(self, name):
+        """the three packing attributes name three different encoders: at most one of them is on"""
+        on = [k for k in ("pack_text", "pack_text_causal", "pack_text_rotary") if k != name and getattr(self, "_" + k)]
+        if on:
+            raise ValueError(f"CLIP.{name}: CLIP.{on[0]} is already on (a model has one text encoder: one of pack_text, pack_text_causal, pack_text_rotary)")
 
     def _packed_layout(self, text, text_mask=None):
         """the layout the packed tower of this model takes for a token batch (device tokens: one read of its row count, packing.text_layout)"""
@@ -579,17 +623,17 @@ class CLIP(nn.Module):
         count, packing.text_layout) and returns the CLS rows."""
         text_args = (text,) if self.text_encode_without_mask else (text, text_mask)
         text_kwargs = None
-        if self._pack_text or self._pack_text_causal:
-            name = "pack_text" if self._pack_text else "pack_text_causal"
-            (self._check_pack_text if self._pack_text else self._check_pack_text_causal)()       # (dropout and train / eval mode are only known now)
+        if self._pack_text or self._pack_text_causal or self._pack_text_rotary:
+            name = "pack_text" if self._pack_text else "pack_text_causal" if self._pack_text_causal else "pack_text_rotary"
+            getattr(self, "_check_" + name)()                  # (dropout and train / eval mode are only known now)
             if not cls_row_only:
                 raise NotImplementedError(f"CLIP.{name} is not available with return_encodings=True (the encoding of every row is returned)")
             text_kwargs = dict(layout=layout if layout is not None else self._packed_layout(text, text_mask))
             if self.pack_text_pool_last:
-                text_kwargs["pool_row"] = 0 if self._pack_text else "eos"
+                text_kwargs["pool_row"] = "eos" if self._pack_text_causal else 0
             return text_args, text_kwargs
         if layout is not None:
-            raise ValueError("text_layout was passed but CLIP.pack_text (or pack_text_causal) is off")
+            raise ValueError("text_layout was passed but CLIP.pack_text (or pack_text_causal / pack_text_rotary) is off")
         if (cls_row_only and self.prune_unused_rows and isinstance(self.text_transformer, TextTransformer) and self.text_has_cls_token
                 and not self.text_causal_mask):
             text_kwargs = dict(pool_row=0)
@@ -761,7 +805,7 @@ class CLIP(nn.Module):
         aug_image=None,
         text_layout=None
     ):
-        """text_layout (not a reference keyword; needs `pack_text`, or `pack_text_causal` with has_cls=False, eos_id=text_eos_id): packing.text_layout(text, pad_id=text_pad_id) built ahead of time, e.g. from
+        """text_layout (not a reference keyword; needs `pack_text` / `pack_text_rotary`, or `pack_text_causal` with has_cls=False, eos_id=text_eos_id): packing.text_layout(text, pad_id=text_pad_id) built ahead of time, e.g. from
         the loader's CPU tokens -- the step then reads nothing back from the device.  Augmented texts get their own layout here, through the same code."""
         batch, device = text.shape[0], text.device
 

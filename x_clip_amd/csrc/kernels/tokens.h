@@ -461,6 +461,60 @@ __global__ __launch_bounds__(256) void rotary_pairs_kernel(T* __restrict__ X, lo
     }
 }
 
+// the two kernels above for rows that carry their own position: token position = pos[row] (int32 [rows]) instead of row % n.  The packed
+// text tower keeps only the rows the key mask keeps, so a row's dense index says nothing about where it stood in its sample
+// (packing.TextLayout.pos does; 0 = the CLS row).  The same items, the same angle (float)pos * inv_freq[j] through the same sincosf and
+// the same expressions: where pos[row] == row % n the result is the dense kernels' bit for bit (the tests hold them to torch.equal).
+template <typename T>
+__global__ __launch_bounds__(256) void rotary_pos_kernel(T* __restrict__ X, long ld, long rows, const int* __restrict__ posv, int slots,
+                                                         int slot_width, const float* __restrict__ inv_freq, float sign) {
+    constexpr int VEC = Elem<T>::VEC;
+    constexpr int HALF = 16;                                   // ROT / 2
+    constexpr int CPH = HALF / VEC;                            // chunks per half: 2 (bf16) / 4 (fp32)
+    const long items = rows * slots * CPH;
+    for (long it = (long)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += (long)gridDim.x * blockDim.x) {
+        const int c = (int)(it % CPH);
+        const long rs = it / CPH;
+        const int slot = (int)(rs % slots);
+        const long row = rs / slots;
+        const float pos = (float)posv[row];
+        T* p = X + row * ld + slot * slot_width + c * VEC;
+        float a[VEC], b[VEC];
+        load_vec<T>(p, a);                                     // features j      = c VEC + (0 .. VEC-1)
+        load_vec<T>(p + HALF, b);                              // features j + 16
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            float sn, cs;
+            sincosf(pos * inv_freq[c * VEC + e], &sn, &cs);
+            sn *= sign;
+            const float x1 = a[e], x2 = b[e];
+            a[e] = x1 * cs - x2 * sn;
+            b[e] = x2 * cs + x1 * sn;
+        }
+        store_vec<T>(p, a);
+        store_vec<T>(p + HALF, b);
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void rotary_pos_pairs_kernel(T* __restrict__ X, long ld, long rows, const int* __restrict__ posv, int slots,
+                                                               int slot_width, int half, const float* __restrict__ inv_freq, float sign) {
+    const long items = rows * slots * half;
+    for (long it = (long)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += (long)gridDim.x * blockDim.x) {
+        const int j = (int)(it % half);
+        const long rs = it / half;
+        const int slot = (int)(rs % slots);
+        const long row = rs / slots;
+        T* p = X + row * ld + slot * slot_width + j;
+        float sn, cs;
+        sincosf((float)posv[row] * inv_freq[j], &sn, &cs);
+        sn *= sign;
+        const float x1 = to_f32(p[0]), x2 = to_f32(p[half]);
+        p[0] = from_f32<T>(x1 * cs - x2 * sn);
+        p[half] = from_f32<T>(x2 * cs + x1 * sn);
+    }
+}
+
 // ---- feed-forward dropout (reference nn.Dropout between the inner LayerNorm and the second Linear, x_clip.py:193-194) -------------
 // y[i] = x[i] * keep(i) / (1 - p) over a contiguous [n] tensor, keep from drop_hash(seed, i) (common.h).  The same launch on the
 // gradient is the backward.  In place is fine.  One 16-byte chunk per lane.

@@ -1028,6 +1028,29 @@ int xclip_rotary(void* x, int64_t ld, int64_t rows, int64_t n, int64_t slots, in
     return check_launch(__func__);
 }
 
+// xclip_rotary for rows that carry their own position (the packed text tower: pos = TextLayout.pos); the launch sizes of xclip_rotary
+int xclip_rotary_pos(void* x, int64_t ld, int64_t rows, const int32_t* pos, int64_t slots, int64_t slot_width, int64_t rot, const float* inv_freq,
+                     int inverse, int dtype, void* stream) {
+    XC_REQUIRE(dtype_ok(dtype), "bad dtype");
+    XC_REQUIRE(slot_width == 64 || slot_width == 128, "head slots are 64 or 128 wide");
+    XC_REQUIRE(rot >= 2 && rot <= 32 && rot % 2 == 0, "rot = min(dim_head, 32) rotated features per head: even, 2 .. 32");
+    XC_REQUIRE(rows >= 0 && slots > 0 && ld >= slots * slot_width && ld % vec_of(dtype) == 0, "bad shape");
+    if (rows == 0) return 0;                                         // (an empty packed batch: its arrays have no address)
+    XC_REQUIRE(x && aligned16(x) && inv_freq && pos, "null or misaligned pointer");
+    const int64_t per_slot = rot == 32 ? 16 / vec_of(dtype) : rot / 2;      // items of a head slot: 16-byte chunk pairs / element pairs
+    int64_t blocks = (rows * slots * per_slot + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    dim3 grid((unsigned)blocks), block(256);
+    const float sign = inverse ? -1.0f : 1.0f;
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        if (rot != 32)                                               // narrow heads: element pairs
+            hipLaunchKernelGGL((rotary_pos_pairs_kernel<T>), grid, block, 0, (hipStream_t)stream, (T*)x, (long)ld, (long)rows, (const int*)pos, (int)slots, (int)slot_width, (int)(rot / 2), inv_freq, sign);
+        else
+            hipLaunchKernelGGL((rotary_pos_kernel<T>), grid, block, 0, (hipStream_t)stream, (T*)x, (long)ld, (long)rows, (const int*)pos, (int)slots, (int)slot_width, inv_freq, sign);
+    });
+    return check_launch(__func__);
+}
+
 // the 256 x 256 bf16 kernels behind xclip_gemm, on the plan's K slices.  reduce = false: a split-K problem leaves its fp32 slabs in
 // g.workspace for the caller (alpha not applied).
 static int gemm2_run(const GemmArgs& g, int splits, int k_per_split, bool reduce, hipStream_t st) {

@@ -201,7 +201,9 @@ def _attn_forward(h: Tensor, W: LayerWeights, c: _Pass, seed: int):
     M, D = h.shape
     spec, inner = c.spec, c.spec.inner
     qkv = ops.gemm(h, W.w_qkv, M, 3 * inner, D)                                        # to_qkv            :216
-    if c.layout is not None:                                   # samples of different lengths, end to end: no mask, no rotary, no dropout (text_encode_packed)
+    if c.layout is not None:                                   # samples of different lengths, end to end: no mask, no dropout (text_encode_packed)
+        if spec.rotary is not None:                            # q, k, v rotated by the position the row had in its sample, not by its packed index  :221-223
+            ops.rotary_pos_(qkv, c.layout.pos, spec.rotary, head_dim=spec.head_slot)
         fwd = ops.attention_varlen_causal_fwd if spec.causal else ops.attention_varlen_fwd      # (causal: key j <= query i by packed row)
         o, lse = fwd(qkv, c.layout.cu, c.layout.max_len, spec.heads, spec.scale, spec.head_slot)
         return qkv, o, lse
@@ -270,7 +272,9 @@ def _attn_backward(do: Tensor, t: LayerTape, c: _Pass, seed: int) -> Tensor:
 def _qkv_backward(dqkv: Tensor, t: LayerTape, W: LayerWeights, need: LayerWeights, c: _Pass, sg: _SideGemm):
     """gradient w.r.t. the packed rotated qkv (rotated back in place) -> (gradient w.r.t. the PreNorm output h, dWqkv)"""
     (M, D), N = t.h.shape, dqkv.shape[1]
-    if c.spec.rotary is not None:
+    if c.spec.rotary is not None and c.layout is not None:
+        ops.rotary_pos_(dqkv, c.layout.pos, c.spec.rotary, inverse=True, head_dim=c.spec.head_slot)
+    elif c.spec.rotary is not None:
         ops.rotary_(dqkv, c.n, c.spec.rotary, inverse=True, head_dim=c.spec.head_slot)      # the saved qkv is the rotated one; R^T maps its gradient back
     dh = ops.gemm(dqkv, W.w_qkv, M, D, N, b_kmajor=True)
     return dh, sg.wgrad(dqkv, t.h, N, D, M, W.w_qkv) if need.w_qkv else None
@@ -401,6 +405,11 @@ def _layer_forward_pooled_packed(x: Tensor, W: LayerWeights, c: _Pass):
     hc = ops.gather_rows(h, first)
     q = ops.gemm(hc, W.w_qkv[:inner], B, inner, D)                                     # to_qkv: the query third on B rows,
     kv = ops.gemm(h, W.w_qkv[inner:], R, 2 * inner, D)                                 # keys | values on all R      :216
+    if spec.rotary is not None:
+        # keys and values rotated at their positions; the query is the CLS row, position 0: the angle 0, sincosf(0) = (0, 1) exactly -- the
+        # identity, as in the dense pooled layer at row == 0
+        assert lay.has_cls and not lay.ends_at_eos, "rotary in the packed tower: the pooled row is the CLS row at position 0"
+        ops.rotary_pos_(kv, lay.pos, spec.rotary, head_dim=spec.head_slot)
     oc, lse = ops.attention_pool_varlen_fwd(q, kv, lay.cu, spec.heads, spec.scale, spec.head_slot)
     p = ops.gemm(oc, W.w_out, B, D, inner)                                             # from here on: B rows
     x2, ff = _ffn_forward(p, xc, W, c, 0)
@@ -416,6 +425,9 @@ def _layer_backward_pooled_packed(dx2: Tensor, t: LayerTape, W: LayerWeights, ne
     d_out = sg.wgrad(dp, t.o, D, inner, B, W.w_out) if need.w_out else None
     doc = ops.gemm(dp, W.w_out, B, inner, D, b_kmajor=True)
     dq, dkv = ops.attention_pool_varlen_bwd(q, kv, lay.cu, t.o, doc, t.lse, spec.heads, spec.scale, spec.head_slot)
+    if spec.rotary is not None:
+        assert lay.has_cls and not lay.ends_at_eos, "rotary in the packed tower: the pooled row is the CLS row at position 0"
+        ops.rotary_pos_(dkv, lay.pos, spec.rotary, inverse=True, head_dim=spec.head_slot)    # the saved kv is the rotated one; R^T maps its gradient back
     # d h = dkv W_kv on every row, + dq W_q on the CLS rows
     dh = ops.gemm(dkv, W.w_qkv[inner:], R, D, 2 * inner, b_kmajor=True)
     ops.rows_add_at(dh, first, ops.gemm(dq, W.w_qkv[:inner], B, D, inner, b_kmajor=True))
@@ -665,8 +677,10 @@ def text_encode_packed(layout, E: Tensor, P: Optional[Tensor], cls: Optional[Ten
     eos = cls is None and spec.causal and layout.ends_at_eos and not layout.has_cls
     if cls is None and not eos:
         raise NotImplementedError("pack_text: the packed text tower returns the CLS row (text_has_cls_token=True)")
-    if spec.rotary is not None or (spec.causal and not eos) or spec.attn_dropout > 0.0 or spec.ff_dropout > 0.0:
-        raise NotImplementedError("pack_text: no rotary embedding (text_rotary_pos_emb), causal mask (text_causal_mask) or dropout in the packed text tower")
+    # rotary (CLIP.pack_text_rotary): the rows are rotated by layout.pos (xclip_rotary_pos); a rotary encoder has a CLS row and no position table
+    if (spec.rotary is not None and (eos or P is not None)) or (spec.causal and not eos) or spec.attn_dropout > 0.0 or spec.ff_dropout > 0.0:
+        raise NotImplementedError("pack_text: no rotary embedding (text_rotary_pos_emb) beside a position table or the causal encoder, no causal mask "
+                                  "(text_causal_mask) without an EOS layout and no dropout in the packed text tower")
     if not eos and (not layout.has_cls or layout.ends_at_eos or layout.R < layout.batch):
         raise ValueError("pack_text: the layout must keep a CLS row per sample (text_layout(..., has_cls=True))")
     if eos and layout.R < layout.batch:

@@ -1314,6 +1314,18 @@ def rotary_(x: Tensor, n: int, inv_freq: Tensor, inverse: bool = False, head_dim
     return x
 
 
+def rotary_pos_(x: Tensor, pos: Tensor, inv_freq: Tensor, inverse: bool = False, head_dim: int = 64) -> Tensor:
+    """rotary_ on rows that carry their own position: pos int32 [rows] (packing.TextLayout.pos of a packed text batch) instead of row % n.
+    Where pos[r] == r % n the same bits as rotary_(x, n, ...)"""
+    _dev_check(x, pos, inv_freq)
+    assert x.dim() == 2 and x.stride(1) == 1 and head_dim in (64, 128) and x.shape[1] % head_dim == 0
+    assert pos.dtype == torch.int32 and pos.dim() == 1 and pos.is_contiguous() and pos.numel() == x.shape[0]
+    assert inv_freq.dtype == torch.float32 and 1 <= inv_freq.numel() <= 16 and inv_freq.is_contiguous()
+    _lib.check(_lib.lib().xclip_rotary_pos(x.data_ptr(), x.stride(0), x.shape[0], pos.data_ptr(), x.shape[1] // head_dim, head_dim,
+                                           2 * inv_freq.numel(), inv_freq.data_ptr(), int(inverse), dtype_code(x), _stream(x)), "xclip_rotary_pos")
+    return x
+
+
 def dwconv4s2_fwd(x: Tensor, w: Tensor) -> Tensor:
     """depthwise 4x4 / stride 2 / pad 1 convolution over the token grid: x [b, h*h, C], w [C, 1, 4, 4] -> [b, (h/2)^2, C]
     (first stage of `downsample_image_embeds`, x_clip.py:560-568)"""

@@ -12,6 +12,9 @@ The causal encoder (`CLIP.pack_text_causal`: no CLS row, a causal mask, read at 
 has_cls=False, eos_id=...)`: under the causal mask a row behind the first EOS is a key of no row that is read either, so the layout ends every
 sample at that token and the pooled row is the sample's last, cu[s+1] - 1 (`TextLayout.ends_at_eos`).
 
+The rotary encoder (`CLIP.pack_text_rotary`) takes the plain layout: `pos` is the position every kept row had in its padded sample, which is
+what its q, k and v are rotated by (xclip_rotary_pos) -- a pad dropped in mid-sequence leaves the positions behind it unchanged.
+
 Built from CPU tokens the layout costs no device synchronisation: `R` and `max_len` are counted on the host and the index tensors are copied
 to the device asynchronously by `.to(device)`.  Built from DEVICE tokens -- the implicit path when `pack_text` is on and no layout is passed --
 it reads `R` and `max_len` back ONCE per call (one small device-to-host copy, the same kind of read the ragged multi-rank gather of
