@@ -20,7 +20,7 @@ extern "C" {
 #endif
 
 enum { XCLIP_F32 = 0, XCLIP_BF16 = 1 };
-#define XCLIP_ABI_VERSION 34
+#define XCLIP_ABI_VERSION 35
 
 int xclip_abi_version(void);
 const char* xclip_last_error(void);
@@ -142,6 +142,14 @@ int xclip_cast_from_f32(const float* src, void* dst, int64_t count, float scale,
  * forward (0,0), dgrad (0,1), wgrad (1,1).  `workspace` (fp32 split-K slabs, may be NULL) of
  * xclip_gemm_workspace_bytes(...) bytes lets long contractions (wgrad) fill the chip. */
 int64_t xclip_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K, int dtype);
+/* Which kernel family xclip_gemm gives a product of this description (a pure host query: nothing is launched, no pointer is read):
+ *   0 the 64 x 64 latency kernel, 1 the 256 x 256 LDS-DMA kernels, 2 the same with the row tail cut into a split-K problem, 3 the generic
+ *   128 x 128 register-staged kernel -- which takes whatever the others refuse (fp32, K % 64 != 0, M % 8 != 0, M or N < 128) and is several
+ *   times slower on the large bf16 products of a tower.  has_bias_or_rows: bias or addrows given; has_residual: residual given;
+ *   workspace_bytes: what the caller would offer.  -1 for a description xclip_gemm refuses.  M = the row count of a packed text batch decides the route of every product of its tower:
+ *   packing.text_layout(row_multiple=256) exists to keep that count on routes 1 / 2. */
+int xclip_gemm_route(int a_kmajor, int b_kmajor, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int has_bias_or_rows,
+                     int has_residual, int64_t workspace_bytes, int dtype);
 int xclip_gemm(int a_kmajor, int b_kmajor, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
                int64_t M, int64_t N, int64_t K, float alpha, const void* bias, const void* residual, int64_t ldr,
                const void* addrows, const int32_t* rowidx, int64_t ld_add, void* workspace, int64_t workspace_bytes,

@@ -48,6 +48,7 @@ _SIGNATURES = {
     "xclip_sort_ids": (c_int, [P, L, L, P, P, P, L, P]),
     "xclip_cast_from_f32": (c_int, [P, P, L, F, I, P]),
     "xclip_gemm_workspace_bytes": (c_int64, [L, L, L, I]),
+    "xclip_gemm_route": (c_int, [I, I, L, L, L, L, L, I, I, L, I]),
     "xclip_gemm_small_limit": (c_int64, [L]),
     "xclip_gemm": (c_int, [I, I, P, L, P, L, P, L, L, L, L, F, P, P, L, P, P, L, P, L, I, P]),
     "xclip_ffn_dgrad_geglu_ok": (c_int, [L, L, L, I]),
@@ -118,7 +119,7 @@ _SIGNATURES = {
     "xclip_grad_accumulate": (c_int, [P, L, L, I, P, I, P]),
 }
 EXPORTS = tuple(_SIGNATURES)
-ABI_VERSION = 34
+ABI_VERSION = 35
 
 
 def _bind(path: str):

@@ -469,6 +469,11 @@ class CLIP(nn.Module):
         # padded sample (TextLayout.pos, xclip_rotary_pos) instead of by its dense row index.  Off: every launch as before (pack_text itself goes
         # on refusing a rotary model)
         self._pack_text_rotary = False
+        # opt-in, only read where one of the three packing attributes is on: None, or a positive int (256 recommended) -- the layouts this model
+        # builds itself (no text_layout passed; the augmented texts) get their row count rounded up to that multiple (packing.text_layout
+        # row_multiple): the tower's GEMMs have M = K = that count, and a count that is no multiple of 8 sends every large one of them to the
+        # generic kernel.  The surplus rows are filler: finite forward, exactly zero backward.  A layout passed in carries its own multiple
+        self._pack_text_row_multiple = None
         # >1: the text batch runs through the text tower in that many slices, each on its own HIP stream.  The tower alternates
         # MFMA-bound GEMMs with HBM-bound row kernels; with two slices in flight one slice's LayerNorm / GEGLU kernels (no LDS, few
         # registers: they fit on a CU beside a persistent GEMM work-group) run under the other slice's GEMMs.  Encoders are row
@@ -600,6 +605,15 @@ class CLIP(nn.Module):
         if why is not None:
             raise NotImplementedError(f"CLIP.pack_text_rotary is not available with {why}")
 
+    @property
+    def pack_text_row_multiple(self):
+        return self._pack_text_row_multiple
+
+    @pack_text_row_multiple.setter
+    def pack_text_row_multiple(self, multiple):
+        from .packing import _check_row_multiple
+        self._pack_text_row_multiple = _check_row_multiple(multiple, "CLIP.pack_text_row_multiple")
+
     def _one_packing(self, name):
         """the three packing attributes name three different encoders: at most one of them is on"""
         on = [k for k in ("pack_text", "pack_text_causal", "pack_text_rotary") if k != name and getattr(self, "_" + k)]
@@ -610,8 +624,8 @@ class CLIP(nn.Module):
         """the layout the packed tower of this model takes for a token batch (device tokens: one read of its row count, packing.text_layout)"""
         from .packing import text_layout
         if self._pack_text_causal:
-            return text_layout(text, self.text_pad_id, mask=text_mask, has_cls=False, eos_id=self.text_eos_id)
-        return text_layout(text, self.text_pad_id, mask=text_mask)
+            return text_layout(text, self.text_pad_id, mask=text_mask, has_cls=False, eos_id=self.text_eos_id, row_multiple=self._pack_text_row_multiple)
+        return text_layout(text, self.text_pad_id, mask=text_mask, row_multiple=self._pack_text_row_multiple)
 
     # ---- what forward and the one-tower entry points share (x_clip.py:650-715) ----
     def _text_tower_call(self, text, text_mask, cls_row_only, layout=None):

@@ -17,7 +17,8 @@
 //                                    [rows, 2 * heads * HS], sample s owns rows cu[s] .. cu[s+1] (cu int32 [batch + 1]) and sees all of them --
 //                                    a masked key has probability exactly 0 in the dense form, so dropping it changes nothing; dkv
 //                                    [rows, 2 * heads * HS], a row written by the unit that owns it; a unit of length 0 writes out = 0, lse = 0,
-//                                    dq = 0 and no dkv row
+//                                    dq = 0 and no dkv row; rows [cu[batch], rows), which no sample owns (filler), get zeros from the last
+//                                    sample's units, so every row of dkv is written
 //   * plain varlen (attention_varlen.h attn_varlen_plain_fwd_kernel): every row of a packed qkv as the query of its own sample
 //   out [batch, heads * HS], lse [batch, heads] (natural log, of the scaled scores); backward: dq [batch, heads * HS], a key's dK = dS q,
 //   dV = P dO (one query's outer products)
@@ -233,10 +234,26 @@ __global__ __launch_bounds__(256) void attn_pool_varlen_fwd_kernel(AttnPoolVarle
     ApUnit<T> u;
     if (attn_pool_varlen_unit<T, HS>(p, u)) ap_fwd_unit<T, HS>(u, p.scale);
 }
+// Filler rows [cu[batch], rows) of dkv (a layout whose row count was rounded up, packing.text_layout(row_multiple=)) belong to no unit: the
+// wave of the LAST sample's head h zeroes that head's key and value slots there, behind its own stores, so that every row of dkv is written
+template <typename T, int HS>
+XC_DEV void apv_zero_filler(const AttnPoolVarlenParams& p) {
+    const long bh = (long)blockIdx.x * 4 + wave_id();
+    if ((int)(bh / p.heads) != p.batch - 1) return;
+    constexpr int VEC = Elem<T>::VEC, CH = HS / VEC;
+    const int h = (int)(bh % p.heads), inner = p.heads * HS;
+    int r0 = p.cu[p.batch];
+    r0 = r0 > 0 ? r0 : 0;
+    T* d = static_cast<T*>(p.dkv) + (long)h * HS;
+    for (long i = lane_id(); i < (long)(p.rows - r0) * 2 * CH; i += 64) {
+        const int rem = (int)(i % (2 * CH));
+        st16(d + (r0 + i / (2 * CH)) * 2 * inner + (long)(rem / CH) * inner + (rem % CH) * VEC, zero16());
+    }
+}
 template <typename T, int HS>
 __global__ __launch_bounds__(256) void attn_pool_varlen_bwd_kernel(AttnPoolVarlenParams p) {
     ApUnit<T> u;
-    if (attn_pool_varlen_unit<T, HS>(p, u)) ap_bwd_unit<T, HS>(u, p.scale);
+    if (attn_pool_varlen_unit<T, HS>(p, u)) { ap_bwd_unit<T, HS>(u, p.scale); apv_zero_filler<T, HS>(p); }
 }
 
 }  // namespace xc

@@ -9,6 +9,9 @@
 //   dqkv [R, 3, heads, HS]   fully overwritten
 // Every key of a sample is visible to every query of that sample and to no other: no mask, no causal flag, no dropout.  A work-group (or
 // wave) only ever stores rows of the unit it owns, so nothing is written outside [0, R); no atomics, a fixed summation order.
+// EVERY row [0, R) is written: R may exceed cu[batch] (packing.text_layout(row_multiple=) rounds the row count up so that the GEMMs around
+// the attention get an M their fast kernels take), and the FILLER rows [cu[batch], R), which no sample owns, get out = 0, lse = 0, dqkv = 0 in
+// the same launch -- by the units of the last sample (head-resident, av_zero_filler) or by the row's own waves (plain, av_plain_filler).
 // The *_causal_* kernels are the same over the same arrays with ONE more rule (the autoregressive text encoder, x_clip.py:231-234): key row j
 // is visible to query row i of its sample iff j <= i, by PACKED row index -- kept rows keep their order, so that is the dense rule on the
 // rows that exist.  A row's lse is then over keys [cu[s], row], and a row sees at least itself.
@@ -50,6 +53,24 @@ XC_DEV int av_sample_of(const int* cu, int batch, int r) {
     return lo;
 }
 
+// A wave whose row lies behind the last sample (r >= cu[batch]: a filler row of a layout whose row count was rounded up) owns no unit: it
+// zeroes its head's slot of that row -- out and lse (forward) or the three slots of dqkv (BWD) -- with 16-byte stores and leaves before
+// the sample search, whose invariant needs r < cu[batch].  -> true: the row was filler
+template <typename T, int HS, bool BWD>
+XC_DEV bool av_plain_filler(const AttnVarlenParams& p, int r, int h) {
+    if (r < p.cu[p.batch]) return false;
+    constexpr int VEC = Elem<T>::VEC, CH = HS / VEC;
+    const int lane = lane_id(), inner = p.heads * HS;
+    if (BWD) {
+        T* d = static_cast<T*>(p.dqkv) + (long)r * 3 * inner + (long)h * HS;
+        for (int i = lane; i < 3 * CH; i += 64) st16(d + (long)(i / CH) * inner + (i % CH) * VEC, zero16());
+    } else {
+        if (lane < CH) st16(static_cast<T*>(p.out) + (long)r * inner + (long)h * HS + lane * VEC, zero16());
+        if (lane == 0) p.lse[(long)h * p.rows + r] = 0.f;
+    }
+    return true;
+}
+
 // the unit of wave blockIdx.x * 4 + wave_id(): row r of head h as the QUERY of its own sample's keys, all of them visible; false: the wave
 // is past the last unit and leaves whole (no barriers anywhere).  attention_pool.h's ApUnit with K / V in the same array as the query
 // (CAUSAL: the keys behind the row are hidden, kvis = r + 1)
@@ -58,6 +79,7 @@ XC_DEV bool av_plain_unit(const AttnVarlenParams& p, ApUnit<T>& u) {
     const long unit = (long)blockIdx.x * 4 + wave_id();
     if (unit >= (long)p.rows * p.heads) return false;
     const int r = (int)(unit / p.heads), h = (int)(unit % p.heads);
+    if (av_plain_filler<T, HS, false>(p, r, h)) return false;
     const int s = av_sample_of(p.cu, p.batch, r);
     const int inner = p.heads * HS, k0 = p.cu[s], k1 = p.cu[s + 1];
     const long ldq = 3L * inner, at = (long)r * inner + (long)h * HS;
@@ -84,6 +106,7 @@ __global__ __launch_bounds__(256) void attn_varlen_plain_bwd_kernel(AttnVarlenPa
     const long unit = (long)blockIdx.x * 4 + wave_id();
     if (unit >= (long)p.rows * p.heads) return;
     const int r = (int)(unit / p.heads), h = (int)(unit % p.heads);
+    if (av_plain_filler<T, HS, true>(p, r, h)) return;
     const int s = av_sample_of(p.cu, p.batch, r);
     const int k0 = p.cu[s], k1 = p.cu[s + 1];
     const int kend = CAUSAL ? r + 1 : k1;                      // the keys row r sees: [k0, kend)
@@ -176,25 +199,46 @@ XC_DEV bool av_unit(const AttnVarlenParams& p, A3Unit& u) {
                 reinterpret_cast<bf16_t*>(p.out), reinterpret_cast<bf16_t*>(p.dqkv), p.lse + (long)hh * p.rows + row0, row0, n, p.heads, hh);
     return true;                                               // (no key mask, abl = the literal 0: a3_unit's defaults)
 }
+// Filler rows [cu[batch], rows): the units of the LAST sample zero their own head's slots there after the body's stores -- 16-byte stores
+// spread over all the work-group's threads (every wave leaves the bodies: the surplus ones wait at their barriers only), the head's lse run with
+// one float per thread.  BWD: the three slots of dqkv; otherwise out and lse.  No filler: zero iterations, nothing read but cu[batch].
+template <bool BWD>
+XC_DEV void av_zero_filler(const AttnVarlenParams& p) {
+    const int bh = xcd_remap(blockIdx.x, p.batch * p.heads);
+    if (bh / p.heads != p.batch - 1) return;                   // (uniform)
+    const int hh = bh % p.heads;
+    int r0 = uniform(p.cu[p.batch]);
+    r0 = r0 > 0 ? r0 : 0;                                      // a cu that does not describe the array: never a row before the first
+    const int nfill = p.rows - r0;
+    const long ldo = (long)p.heads * ATT_DH;
+    constexpr int CH = ATT_DH / 8, PER_ROW = (BWD ? 3 : 1) * CH;         // 16-byte chunks of a head slot, of a row's slots
+    bf16_t* base = reinterpret_cast<bf16_t*>(BWD ? p.dqkv : p.out) + (long)hh * ATT_DH;
+    for (long i = threadIdx.x; i < (long)nfill * PER_ROW; i += blockDim.x) {
+        const int row = r0 + (int)(i / PER_ROW), rem = (int)(i % PER_ROW);
+        st16(base + (long)row * (BWD ? 3 : 1) * ldo + (rem / CH) * ldo + (rem % CH) * 8, zero16());
+    }
+    if (!BWD)
+        for (int i = threadIdx.x; i < nfill; i += blockDim.x) p.lse[(long)hh * p.rows + r0 + i] = 0.f;
+}
 // blockDim = 64 a3_waves(max_len): every length up to max_len finds the waves attn3_fwd_kernel would have been launched with (a3_waves is
 // monotonic up to its cooperative-tail dip, which max_len's own value covers); wave w >= a3_waves(n) owns no query block of this unit
 // (a3_fwd_unit's RAGGED).
 __global__ __launch_bounds__(576) XC_FOUR_WAVES_PER_SIMD void attn_varlen_fwd_kernel(AttnVarlenParams p) {
     A3Unit u;
-    if (av_unit(p, u)) a3_fwd_unit<false, true>(u, p.scale);
+    if (av_unit(p, u)) { a3_fwd_unit<false, true>(u, p.scale); av_zero_filler<false>(p); }
 }
 __global__ __launch_bounds__(256) void attn_varlen_bwd_kernel(AttnVarlenParams p) {
     A3Unit u;
-    if (av_unit(p, u)) a3_bwd_unit<false>(u, p.scale);
+    if (av_unit(p, u)) { a3_bwd_unit<false>(u, p.scale); av_zero_filler<true>(p); }
 }
 // the causal twins: the same unit, launch sizing and bounds; the bodies' CAUSAL skips the sub-tiles above the diagonal
 __global__ __launch_bounds__(576) XC_FOUR_WAVES_PER_SIMD void attn_varlen_causal_fwd_kernel(AttnVarlenParams p) {
     A3Unit u;
-    if (av_unit(p, u)) a3_fwd_unit<true, true, false>(u, p.scale);      // (no key mask in a packed unit)
+    if (av_unit(p, u)) { a3_fwd_unit<true, true, false>(u, p.scale); av_zero_filler<false>(p); }      // (no key mask in a packed unit)
 }
 __global__ __launch_bounds__(256) void attn_varlen_causal_bwd_kernel(AttnVarlenParams p) {
     A3Unit u;
-    if (av_unit(p, u)) a3_bwd_unit<true>(u, p.scale);
+    if (av_unit(p, u)) { a3_bwd_unit<true>(u, p.scale); av_zero_filler<true>(p); }
 }
 
 // launch sizes for a batch whose longest sample has max_len rows: every shorter unit fits the same carve.  The backward always carves the

@@ -1121,6 +1121,22 @@ int64_t xclip_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K, int dtype) {
     return gemm_plan(g, dtype, INT64_MAX, -1).workspace_bytes;
 }
 
+// the route of the plan xclip_gemm would execute for a product of this description (a host query: the plan reads which optional terms are
+// there, never through them -- a stand-in address marks them)
+int xclip_gemm_route(int a_kmajor, int b_kmajor, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int has_bias_or_rows,
+                     int has_residual, int64_t workspace_bytes, int dtype) {
+    if (!dtype_ok(dtype) || M <= 0 || N <= 0 || K <= 0 || workspace_bytes < 0) {      // (-1: a code of xclip_gemm's would read as a route)
+        xcapi::fail(__func__, "bad dtype or shape");
+        return -1;
+    }
+    static const char term = 0;
+    GemmArgs g{};
+    g.a_kmajor = a_kmajor; g.b_kmajor = b_kmajor; g.lda = lda; g.ldb = ldb; g.M = M; g.N = N; g.K = K;
+    g.bias = has_bias_or_rows ? &term : nullptr;
+    g.residual = has_residual ? &term : nullptr;
+    return (int)gemm_plan(g, dtype, workspace_bytes, g_small_flop).route;
+}
+
 int xclip_gemm(int a_kmajor, int b_kmajor, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
                int64_t M, int64_t N, int64_t K, float alpha, const void* bias, const void* residual, int64_t ldr,
                const void* addrows, const int32_t* rowidx, int64_t ld_add, void* workspace, int64_t workspace_bytes,

@@ -324,7 +324,8 @@ static int attn_varlen_setup(const char* fn, const void* qkv, const int32_t* cu,
                              int64_t max_len, float scale, int dtype, bool ptrs_ok, xc::AttnVarlenParams& p) {
 #define XC_REQ(cond, msg) do { if (!(cond)) return xcapi::fail(fn, msg); } while (0)
     XC_REQ(xcapi::dtype_ok(dtype), "bad dtype");
-    XC_REQ(batch >= 0 && heads > 0 && rows >= batch && max_len >= 1 && rows <= batch * max_len, "bad shape: every sample has 1 .. max_len rows");
+    // (rows may exceed batch * max_len: the rows behind cu[batch] are filler, owned by no sample -- zeros are written there)
+    XC_REQ(batch >= 0 && heads > 0 && rows >= batch && max_len >= 1, "bad shape: every sample has 1 .. max_len rows");
     XC_REQ(rows * heads < ((int64_t)1 << 31) && rows * 3 * heads * head_dim < ((int64_t)1 << 40), "too many rows");
     XC_REQ(head_dim == 64 || head_dim == 128, "head_dim must be 64 or 128 (narrower / in-between widths are zero-padded by the caller)");
     XC_REQ(ptrs_ok && cu != nullptr, "pointers must be non-null and 16-byte aligned");

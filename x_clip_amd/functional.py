@@ -191,7 +191,11 @@ class _GainGrads:
 # ---- one pre-norm residual block pair (x_clip.py:285-289): the attention block and the feed-forward block -----------------------------
 # c: what a pass shares; seed: the layer's dropout seed (+ 1: the feed-forward block's); need / dg: the layer's `need` flags / gain accumulators
 # layout (packing.TextLayout, or None): the rows are the kept rows of a padded batch laid end to end -- M = layout.R instead of B n; the
-# attention takes the samples' row ranges from layout.cu (attention_varlen.h), everything row-wise runs on the R rows unchanged
+# attention takes the samples' row ranges from layout.cu (attention_varlen.h), everything row-wise runs on the R rows unchanged.
+# Filler rows (layout.kept <= r < layout.R, text_layout(row_multiple=)) are ordinary rows to everything but the attention, which writes
+# zeros there.  The invariant that keeps them out of every result: their activations are FINITE (the embedding of (tok 0, pos 0), then row-wise
+# operations on finite input, attention output 0) and their gradients EXACTLY 0 (dy enters at pooled rows only, dqkv / dkv filler is 0, and the
+# row-wise backwards map a zero row to a zero row) -- so the filler term of every weight gradient is finite x 0.
 _Pass = NamedTuple("_Pass", [("spec", StackSpec), ("B", int), ("n", int), ("mask", Optional[Tensor]), ("layout", object)])
 _Pass.__new__.__defaults__ = (None,)
 
@@ -681,9 +685,9 @@ def text_encode_packed(layout, E: Tensor, P: Optional[Tensor], cls: Optional[Ten
     if (spec.rotary is not None and (eos or P is not None)) or (spec.causal and not eos) or spec.attn_dropout > 0.0 or spec.ff_dropout > 0.0:
         raise NotImplementedError("pack_text: no rotary embedding (text_rotary_pos_emb) beside a position table or the causal encoder, no causal mask "
                                   "(text_causal_mask) without an EOS layout and no dropout in the packed text tower")
-    if not eos and (not layout.has_cls or layout.ends_at_eos or layout.R < layout.batch):
+    if not eos and (not layout.has_cls or layout.ends_at_eos or layout.kept < layout.batch):
         raise ValueError("pack_text: the layout must keep a CLS row per sample (text_layout(..., has_cls=True))")
-    if eos and layout.R < layout.batch:
+    if eos and layout.kept < layout.batch:
         raise ValueError("pack_text_causal: the layout must keep every sample's EOS row")
     if P is not None and layout.n > P.shape[0]:
         raise IndexError(f"text length {layout.n} exceeds max_seq_len {P.shape[0]}")

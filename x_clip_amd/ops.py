@@ -777,7 +777,8 @@ def _attention_varlen_bwd(qkv: Tensor, cu: Tensor, max_len: int, out: Tensor, do
 
 def attention_varlen_fwd(qkv: Tensor, cu: Tensor, max_len: int, heads: int, scale: float, head_dim: int = 64) -> Tuple[Tensor, Tensor]:
     """samples of different lengths laid end to end: qkv [R, 3*heads*head_dim], cu int32 [b + 1] (sample s = rows cu[s] .. cu[s+1], each
-    1 .. max_len long); every key of a sample visible to every query of that sample and to no other -> out [R, heads*head_dim], lse fp32 [heads, R]"""
+    1 .. max_len long); every key of a sample visible to every query of that sample and to no other -> out [R, heads*head_dim], lse fp32 [heads, R].
+    R may exceed cu[b] (packing.text_layout(row_multiple=)): the filler rows behind the last sample get out = 0, lse = 0 (backward: dqkv = 0)"""
     return _attention_varlen_fwd(qkv, cu, max_len, heads, scale, head_dim, False)
 
 
@@ -864,7 +865,7 @@ def attention_pool_varlen_fwd(q: Tensor, kv: Tensor, cu: Tensor, heads: int, sca
 
 def attention_pool_varlen_bwd(q: Tensor, kv: Tensor, cu: Tensor, out: Tensor, dout: Tensor, lse: Tensor, heads: int, scale: float,
                               head_dim: int = 64) -> Tuple[Tensor, Tensor]:
-    """-> dq [b, heads*head_dim], dkv [R, 2*heads*head_dim] (every row a sample owns written)"""
+    """-> dq [b, heads*head_dim], dkv [R, 2*heads*head_dim] (every row written: zeros on the filler rows behind cu[b], which no sample owns)"""
     _dev_check(q, kv, cu, out, dout, lse)
     q, kv, out, dout = _c(q), _c(kv), _c(out), _c(dout)
     R, b = kv.shape[0], cu.numel() - 1
