@@ -20,7 +20,7 @@ extern "C" {
 #endif
 
 enum { XCLIP_F32 = 0, XCLIP_BF16 = 1 };
-#define XCLIP_ABI_VERSION 35
+#define XCLIP_ABI_VERSION 36
 
 int xclip_abi_version(void);
 const char* xclip_last_error(void);
@@ -449,6 +449,20 @@ int xclip_rotary(void* x, int64_t ld, int64_t rows, int64_t n, int64_t slots, in
  * 2 * heads).  rows == 0: nothing is launched. */
 int xclip_rotary_pos(void* x, int64_t ld, int64_t rows, const int32_t* pos, int64_t slots, int64_t slot_width, int64_t rot, const float* inv_freq,
                      int inverse, int dtype, void* stream);
+/* Packed rows <-> dense (sample, position) rows (ABI 36): the step between the packed text tower and a head that indexes by position
+ * (the fine-grained head's `enc_text[:, 1:]`, x_clip.py:704; the MLM head; return_encodings).  cu int32 [batch + 1] and pos int32 [rows] as
+ * x_clip_amd.packing.TextLayout holds them: sample s owns packed rows cu[s] .. cu[s+1], pos strictly ascending inside a sample; rows may
+ * exceed cu[batch] (filler rows, owned by no sample).  packed [rows, dim], dense [batch, n_out, dim], both contiguous, dim a whole number of
+ * 16-byte chunks.
+ *   unpack_rows: dense[s, p - pos0, :] = packed[r, :] for the row r of sample s with pos[r] == p, pos0 <= p < pos0 + n_out; every other
+ *     row of dense = +0.  pos0 = 1, n_out = n drops the CLS row; pos0 = 0, n_out = n + 1 keeps it.
+ *   pack_rows: packed[r, :] = dense[s(r), pos[r] - pos0, :] for r < cu[batch] with pos0 <= pos[r] < pos0 + n_out; every other row of
+ *     packed = +0 (the CLS rows when pos0 = 1, the filler rows).
+ * Each is the other's transpose (= backward).  Every output row is written exactly once in the one launch: no fill in front, no atomics. */
+int xclip_unpack_rows(const void* packed, const int32_t* cu, const int32_t* pos, void* dense, int64_t rows, int64_t batch, int64_t n_out,
+                      int64_t pos0, int64_t dim, int dtype, void* stream);
+int xclip_pack_rows(const void* dense, const int32_t* cu, const int32_t* pos, void* packed, int64_t rows, int64_t batch, int64_t n_out,
+                    int64_t pos0, int64_t dim, int dtype, void* stream);
 /* Similarity regularisation (x_clip.py:773-784): D[r,c] = A[r,c] - C[r,c] for two materialised similarity blocks (text-text and
  * image-image, [rows, cols] in the model dtype, row strides lda / ldc), 0 where c == r + diag_off (the global diagonal);
  * *sumsq_accum += sum D^2 (fp32, of the unrounded differences).  D (row stride ldd, model dtype) is the gradient factor:

@@ -85,6 +85,8 @@ _SIGNATURES = {
     "xclip_layernorm_chain_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, L, L, L, I, P]),
     "xclip_gather_rows": (c_int, [P, L, P, P, L, L, I, P]),
     "xclip_rows_add_at": (c_int, [P, L, P, P, L, L, I, P]),
+    "xclip_unpack_rows": (c_int, [P, P, P, P, L, L, L, L, L, I, P]),
+    "xclip_pack_rows": (c_int, [P, P, P, P, L, L, L, L, L, I, P]),
     "xclip_cross_entropy_fwd": (c_int, [P, L, P, L, L, P, P, I, P]),
     "xclip_cross_entropy_bwd": (c_int, [P, L, P, P, P, L, L, I, P]),
     "xclip_batchnorm_workspace_bytes": (c_int64, [L, L]),
@@ -119,7 +121,7 @@ _SIGNATURES = {
     "xclip_grad_accumulate": (c_int, [P, L, L, I, P, I, P]),
 }
 EXPORTS = tuple(_SIGNATURES)
-ABI_VERSION = 35
+ABI_VERSION = 36
 
 
 def _bind(path: str):

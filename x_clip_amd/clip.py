@@ -208,27 +208,34 @@ class TextTransformer(nn.Module):
         self.cls_token = nn.Parameter(torch.randn(dim)) if not causal else None            # x_clip.py:314
         self.transformer = Transformer(dim, dim_head=dim_head, causal=causal, **kwargs)
 
-    def forward(self, x, mask=None, *, pool_row: Optional[int] = None, layout=None):
+    def forward(self, x, mask=None, *, pool_row: Optional[int] = None, layout=None, rows: bool = False):
         """pool_row = r (not a reference keyword): the caller will read row r of every sample's encoding and nothing else -- the result is
         then [b, dim], and the last layer's row-wise part (to_out, feed-forward, norm_out) runs on those rows alone (functional.stack_forward).
         layout (packing.TextLayout of x under its key mask; CLIP.pack_text, or CLIP.pack_text_rotary for a rotary encoder): the tower runs on the kept rows only and returns the CLS rows [b, dim];
         with pool_row = 0 its last layer is the pooled one as well (CLIP.pack_text_pool_last).
         A causal encoder (CLIP.pack_text_causal) takes a layout that ends every sample at its first EOS token (text_layout(eos_id=)) and returns
         the EOS rows [b, dim] -- what `eos_to_front(...)[:, 0]` reads of the dense encoding; its pooled last layer is asked for with
-        pool_row = "eos" (the row is not a fixed position: 0 keeps meaning position 0)"""
+        pool_row = "eos" (the row is not a fixed position: 0 keeps meaning position 0).
+        rows = True (with a layout; CLIP.pack_text_tokens): the result is the encoding of every packed row, [layout.R, dim] -- what the heads that
+        read token rows take (functional.unpack_rows puts the rows back by position); the last layer is never pooled"""
         t = self.transformer
         pos = self.abs_pos_emb.weight if exists(self.abs_pos_emb) else None
         if layout is not None:
             if layout.batch != x.shape[0] or layout.n != x.shape[1]:
                 raise ValueError(f"text_layout was built for a [{layout.batch}, {layout.n}] token batch, the text is {tuple(x.shape)}")
-            if t.causal:
+            if rows:
+                if pool_row is not None:
+                    raise ValueError("a packed text tower that returns every row (rows=True) does not pool its last layer: pool_row is None")
+            elif t.causal:
                 if pool_row not in (None, "eos"):
                     raise ValueError('a packed causal text tower returns the EOS rows: pool_row is "eos" (the pooled last layer) or None (the dense one)')
             elif pool_row not in (None, 0):
                 raise ValueError("a packed text tower returns the CLS rows: pool_row is 0 (the pooled last layer) or None (the dense one)")
             return XF.text_encode_packed(layout, self.token_emb.weight, pos, self.cls_token, t.stack_params(),
                                          t.spec(rotary=self.rotary_pos_emb.frequencies(x.device) if exists(self.rotary_pos_emb) else None),
-                                         pool_last=pool_row is not None)
+                                         pool_last=pool_row is not None, rows=rows)
+        if rows:
+            raise ValueError("rows=True returns the rows of a packed batch: pass its layout")
         return XF.text_encode(x, mask, self.token_emb.weight, pos, self.cls_token, t.stack_params(),
                               t.spec(rotary=self.rotary_pos_emb.frequencies(x.device) if exists(self.rotary_pos_emb) else None), pool_row=pool_row)
 
@@ -469,7 +476,13 @@ class CLIP(nn.Module):
         # padded sample (TextLayout.pos, xclip_rotary_pos) instead of by its dense row index.  Off: every launch as before (pack_text itself goes
         # on refusing a rotary model)
         self._pack_text_rotary = False
-        # opt-in, only read where one of the three packing attributes is on: None, or a positive int (256 recommended) -- the layouts this model
+        # opt-in, the same for the models whose heads read TOKEN rows (use_all_token_embeds, use_mlm; absolute or rotary positions) and for
+        # return_encodings=True: the tower returns its [R, dim] rows, the fine-grained head's projection and l2-norm run on them, and
+        # xclip_unpack_rows puts them back by (sample, position) where a dense array is needed -- padded positions read as +0, which every
+        # consumer multiplies by the text mask.  The MLM pass shares the call's one layout (TextLayout.with_tokens) and gathers its masked
+        # positions by packed row.  Off: every launch as before (pack_text itself goes on refusing these models)
+        self._pack_text_tokens = False
+        # opt-in, only read where one of the four packing attributes is on: None, or a positive int (256 recommended) -- the layouts this model
         # builds itself (no text_layout passed; the augmented texts) get their row count rounded up to that multiple (packing.text_layout
         # row_multiple): the tower's GEMMs have M = K = that count, and a count that is no multiple of 8 sends every large one of them to the
         # generic kernel.  The surplus rows are filler: finite forward, exactly zero backward.  A layout passed in carries its own multiple
@@ -606,6 +619,36 @@ class CLIP(nn.Module):
             raise NotImplementedError(f"CLIP.pack_text_rotary is not available with {why}")
 
     @property
+    def pack_text_tokens(self) -> bool:
+        return self._pack_text_tokens
+
+    @pack_text_tokens.setter
+    def pack_text_tokens(self, on):
+        if on:
+            self._one_packing("pack_text_tokens")
+            self._check_pack_text_tokens()
+        self._pack_text_tokens = bool(on)
+
+    def _check_pack_text_tokens(self):
+        """pack_text_tokens is the packed tower for the heads that read token rows (the fine-grained head, the MLM head): a model with neither is
+        pointed at pack_text, and what cannot be dropped or has no packed form is out (the message names the option)"""
+        tt = self.text_transformer
+        if not isinstance(tt, TextTransformer):
+            raise NotImplementedError("CLIP.pack_text_tokens is not available with a pluggable text_encoder (only the built-in TextTransformer has a packed form)")
+        if not (self.use_all_token_embeds or self.use_mlm):
+            raise ValueError("CLIP.pack_text_tokens packs the text tower of a model whose heads read token rows (use_all_token_embeds=True or "
+                             "use_mlm=True); for the CLS head set CLIP.pack_text (CLIP.pack_text_rotary / CLIP.pack_text_causal for those encoders)")
+        why = None                                              # (text_causal_mask: refused with either head at construction)
+        if not self.text_has_cls_token or not exists(tt.cls_token):
+            why = "text_has_cls_token=False (the packed rows are put back behind a CLS position)"
+        elif self.text_encode_without_mask:
+            why = "text_encode_without_mask (without a key mask the padded rows are attended to: nothing can be dropped)"
+        elif tt.transformer.training and (tt.transformer.attn_dropout > 0. or tt.transformer.ff_dropout > 0.):
+            why = "attn_dropout / ff_dropout in the text tower (the keep-masks are indexed by dense position)"
+        if why is not None:
+            raise NotImplementedError(f"CLIP.pack_text_tokens is not available with {why}")
+
+    @property
     def pack_text_row_multiple(self):
         return self._pack_text_row_multiple
 
@@ -615,10 +658,11 @@ class CLIP(nn.Module):
         self._pack_text_row_multiple = _check_row_multiple(multiple, "CLIP.pack_text_row_multiple")
 
     def _one_packing(self, name):
-        """the three packing attributes name three different encoders: at most one of them is on"""
-        on = [k for k in ("pack_text", "pack_text_causal", "pack_text_rotary") if k != name and getattr(self, "_" + k)]
+        """the packing attributes name different encoders / heads: at most one of them is on"""
+        on = [k for k in ("pack_text", "pack_text_causal", "pack_text_rotary", "pack_text_tokens") if k != name and getattr(self, "_" + k)]
         if on:
-            raise ValueError(f"CLIP.{name}: CLIP.{on[0]} is already on (a model has one text encoder: one of pack_text, pack_text_causal, pack_text_rotary)")
+            raise ValueError(f"CLIP.{name}: CLIP.{on[0]} is already on (a model has one text encoder: one of pack_text, pack_text_causal, "
+                             "pack_text_rotary, pack_text_tokens)")
 
     def _packed_layout(self, text, text_mask=None):
         """the layout the packed tower of this model takes for a token batch (device tokens: one read of its row count, packing.text_layout)"""
@@ -634,9 +678,18 @@ class CLIP(nn.Module):
         the same loss and gradients up to bf16 rounding order: the other rows of that part are dead in the forward and their gradient is
         exactly zero in the backward).  `prune_unused_rows = False` keeps the dense last layer.
         `pack_text`: the tower gets the packed layout of the batch (`layout`, or built here from the device tokens: one read of its row
-        count, packing.text_layout) and returns the CLS rows."""
+        count, packing.text_layout) and returns the CLS rows.
+        `pack_text_tokens`: the same tower; where the caller reads token rows (not `cls_row_only`) it returns all R of them (`rows=True`)."""
         text_args = (text,) if self.text_encode_without_mask else (text, text_mask)
         text_kwargs = None
+        if self._pack_text_tokens:
+            self._check_pack_text_tokens()                      # (dropout and train / eval mode are only known now)
+            text_kwargs = dict(layout=layout if layout is not None else self._packed_layout(text, text_mask))
+            if not cls_row_only:
+                text_kwargs["rows"] = True
+            elif self.pack_text_pool_last:                      # (an MLM-only model: the contrastive pass is the CLS head)
+                text_kwargs["pool_row"] = 0
+            return text_args, text_kwargs
         if self._pack_text or self._pack_text_causal or self._pack_text_rotary:
             name = "pack_text" if self._pack_text else "pack_text_causal" if self._pack_text_causal else "pack_text_rotary"
             getattr(self, "_check_" + name)()                  # (dropout and train / eval mode are only known now)
@@ -647,7 +700,7 @@ class CLIP(nn.Module):
                 text_kwargs["pool_row"] = "eos" if self._pack_text_causal else 0
             return text_args, text_kwargs
         if layout is not None:
-            raise ValueError("text_layout was passed but CLIP.pack_text (or pack_text_causal / pack_text_rotary) is off")
+            raise ValueError("text_layout was passed but CLIP.pack_text (or pack_text_causal / pack_text_rotary / pack_text_tokens) is off")
         if (cls_row_only and self.prune_unused_rows and isinstance(self.text_transformer, TextTransformer) and self.text_has_cls_token
                 and not self.text_causal_mask):
             text_kwargs = dict(pool_row=0)
@@ -819,15 +872,23 @@ class CLIP(nn.Module):
         aug_image=None,
         text_layout=None
     ):
-        """text_layout (not a reference keyword; needs `pack_text` / `pack_text_rotary`, or `pack_text_causal` with has_cls=False, eos_id=text_eos_id): packing.text_layout(text, pad_id=text_pad_id) built ahead of time, e.g. from
+        """text_layout (not a reference keyword; needs `pack_text` / `pack_text_rotary` / `pack_text_tokens`, or `pack_text_causal` with has_cls=False, eos_id=text_eos_id): packing.text_layout(text, pad_id=text_pad_id) built ahead of time, e.g. from
         the loader's CPU tokens -- the step then reads nothing back from the device.  Augmented texts get their own layout here, through the same code."""
         batch, device = text.shape[0], text.device
 
         text_mask = text != self.text_pad_id                                               # x_clip.py:614
 
+        if self._pack_text_tokens and not exists(text_layout):
+            # ONE layout for the MLM pass and the contrastive pass of this call (device tokens: the one read of its row count)
+            self._check_pack_text_tokens()
+            text_layout = self._packed_layout(text, text_mask)
+
         text_ssl_loss = 0                                                                  # x_clip.py:618-622
         if return_loss and self.use_mlm:
-            text_ssl_loss = self.mlm(text, mask=text_mask)
+            if self._pack_text_tokens:
+                text_ssl_loss = self.mlm(text, mask=text_mask, layout=text_layout)
+            else:
+                text_ssl_loss = self.mlm(text, mask=text_mask)
         image_ssl_loss = 0
         if return_loss and self.use_visual_ssl:
             image_ssl_loss = self.visual_ssl(image)
@@ -862,10 +923,18 @@ class CLIP(nn.Module):
         text_args, text_kwargs = self._text_tower_call(text, text_mask, cls_row_only, text_layout)
 
         enc_text_parts, enc_image = self._encode_towers(text_args, text_kwargs, image, freeze_image_encoder, freeze_text_encoder)
+        # pack_text_tokens with token rows wanted: the tower returned its [R, dim] rows; they go back by (sample, position) as late as possible
+        packed_rows = text_kwargs["layout"] if (text_kwargs is not None and text_kwargs.get("rows")) else None
         if return_encodings:                                                               # x_clip.py:697-698
+            if packed_rows is not None:                        # kept rows: the dense tower's; padded rows (unspecified there): +0
+                return XF.unpack_rows(enc_text_parts[0], packed_rows, 0, text.shape[1] + 1), enc_image
             return self._join_text(enc_text_parts, text), enc_image
 
-        if self.use_all_token_embeds:                                                      # x_clip.py:702-706
+        if self.use_all_token_embeds and packed_rows is not None:
+            assert enc_image.ndim == 3, 'encoded image must have 3 dimensions (batch, seq [height x width], features)'
+            text_embeds = enc_text_parts[0]                    # [R, dim]: projected and normalised per row, unpacked behind that
+            image_embeds = enc_image[:, 1:] if self.visual_has_cls_token else enc_image
+        elif self.use_all_token_embeds:                                                    # x_clip.py:702-706
             enc_text = self._join_text(enc_text_parts, text)
             assert enc_text.ndim == 3, 'encoded text must have 3 dimensions (batch, seq, features)'
             assert enc_image.ndim == 3, 'encoded image must have 3 dimensions (batch, seq [height x width], features)'
@@ -882,6 +951,9 @@ class CLIP(nn.Module):
         if self.extra_latent_projection:
             text_latents_extra = self._text_latents(text_embeds, self.to_text_latent_extra)
             image_latents_extra = self._image_latents(image_embeds, self.to_visual_latent_extra)
+        if self.use_all_token_embeds and packed_rows is not None:                          # `[:, 1:]` (x_clip.py:704) of the rows that exist
+            text_latents = XF.unpack_rows(text_latents, packed_rows, 1, text.shape[1])
+            text_latents_extra = XF.unpack_rows(text_latents_extra, packed_rows, 1, text.shape[1]) if self.extra_latent_projection else text_latents
 
         if return_latents:                                                                 # x_clip.py:728-732
             if self.extra_latent_projection:

@@ -14,6 +14,7 @@
 #include "kernels/attention7.h"
 #include "kernels/attention_pool.h"
 #include "kernels/attention_varlen.h"
+#include "kernels/pack_rows.h"
 
 using namespace xc;
 using namespace xcapi;
@@ -464,6 +465,50 @@ int xclip_attention_pool_varlen_bwd(const void* q, const void* kv, const int32_t
     if (rc != 0 || batch == 0) return rc;
     p.out = const_cast<void*>(out); p.lse = const_cast<float*>(lse); p.dout = dout; p.dq = dq; p.dkv = dkv;
     by_dtype(dtype, [&](auto t) { launch_wave_per_unit<PoolVarlenKernels, typename decltype(t)::type>(p, batch * heads, head_dim, true, (hipStream_t)stream); });
+    return check_launch(__func__);
+}
+
+}  // extern "C"
+
+// ---- packed rows <-> dense (sample, position) rows (kernels/pack_rows.h; in this unit because the pack kernel finds a row's sample with
+// attention_varlen.h's av_sample_of, and the attention headers define kernels that only one unit may hold) ----
+static int pack_rows_check(const char* fn, const void* packed, const int32_t* cu, const int32_t* pos, const void* dense, int64_t rows, int64_t batch,
+                           int64_t n_out, int64_t pos0, int64_t dim, int dtype) {
+#define XC_REQ(cond, msg) do { if (!(cond)) return xcapi::fail(fn, msg); } while (0)
+    XC_REQ(xcapi::dtype_ok(dtype), "bad dtype");
+    XC_REQ(rows >= 0 && batch >= 0 && n_out >= 0 && pos0 >= 0, "bad shape");
+    XC_REQ(dim > 0 && dim % xcapi::vec_of(dtype) == 0, "dim must be a multiple of the 16-byte chunk");
+    XC_REQ(rows < ((int64_t)1 << 31) && batch * n_out < ((int64_t)1 << 31) && pos0 + n_out < ((int64_t)1 << 31) && dim < ((int64_t)1 << 31), "too many rows");
+    XC_REQ(cu != nullptr, "cu must be non-null");
+    XC_REQ((rows == 0 || (packed && pos)) && (batch * n_out == 0 || dense) && xcapi::aligned16(packed) && xcapi::aligned16(dense),
+           "pointers must be non-null and 16-byte aligned");
+    return 0;
+#undef XC_REQ
+}
+
+extern "C" {
+
+int xclip_unpack_rows(const void* packed, const int32_t* cu, const int32_t* pos, void* dense, int64_t rows, int64_t batch, int64_t n_out,
+                      int64_t pos0, int64_t dim, int dtype, void* stream) {
+    const int rc = pack_rows_check(__func__, packed, cu, pos, dense, rows, batch, n_out, pos0, dim, dtype);
+    if (rc != 0 || batch * n_out == 0) return rc;
+    dim3 grid((unsigned)((batch * n_out + 3) / 4)), block(256);
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((unpack_rows_kernel<T>), grid, block, 0, (hipStream_t)stream, (const T*)packed, (const int*)cu, (const int*)pos, (T*)dense,
+                           (int)rows, (int)batch, (int)n_out, (int)pos0, (int)dim);
+    });
+    return check_launch(__func__);
+}
+
+int xclip_pack_rows(const void* dense, const int32_t* cu, const int32_t* pos, void* packed, int64_t rows, int64_t batch, int64_t n_out,
+                    int64_t pos0, int64_t dim, int dtype, void* stream) {
+    const int rc = pack_rows_check(__func__, packed, cu, pos, dense, rows, batch, n_out, pos0, dim, dtype);
+    if (rc != 0 || rows == 0) return rc;
+    dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((pack_rows_kernel<T>), grid, block, 0, (hipStream_t)stream, (const T*)dense, (const int*)cu, (const int*)pos, (T*)packed,
+                           (int)rows, (int)batch, (int)n_out, (int)pos0, (int)dim);
+    });
     return check_launch(__func__);
 }
 

@@ -196,8 +196,35 @@ class _GainGrads:
 # zeros there.  The invariant that keeps them out of every result: their activations are FINITE (the embedding of (tok 0, pos 0), then row-wise
 # operations on finite input, attention output 0) and their gradients EXACTLY 0 (dy enters at pooled rows only, dqkv / dkv filler is 0, and the
 # row-wise backwards map a zero row to a zero row) -- so the filler term of every weight gradient is finite x 0.
+# A packed pass WITH a mask (stack_forward `dense_attention`): the mask is the dense key mask [batch, layout.n + 1] of the layout, and the
+# attention alone runs through the DENSE kernels on the rows put back by position (_attn_dense_on_packed) -- the route of the heads that read
+# token rows wherever the varlen entry points would take their plain form, whose summation order is not the dense kernels'.
 _Pass = NamedTuple("_Pass", [("spec", StackSpec), ("B", int), ("n", int), ("mask", Optional[Tensor]), ("layout", object)])
 _Pass.__new__.__defaults__ = (None,)
+VARLEN_RESIDENT_MAX_LEN = 288          # csrc/kernels/attention3.h A3_MAX_N, as csrc/xclip_attn.hip attn_varlen_resident reads it
+
+
+def varlen_is_head_resident(dtype, head_slot: int, max_len: int) -> bool:
+    """does the varlen attention of a packed pass run attention3.h's head-resident bodies -- the dense bf16 kernels' own, bit for bit on the
+    kept rows under a key mask -- or its plain form (csrc/xclip_attn.hip attn_varlen_resident)?"""
+    return dtype == torch.bfloat16 and head_slot == 64 and max_len <= VARLEN_RESIDENT_MAX_LEN
+
+
+def _attn_dense_on_packed(c: _Pass, qkv: Tensor, o: Optional[Tensor] = None, do: Optional[Tensor] = None, lse: Optional[Tensor] = None):
+    """the dense masked attention on packed rows: qkv [R, 3 inner] (and, backward, o / do [R, inner]) go back to their (sample, position) places
+    (xclip_unpack_rows: +0 where the layout keeps no row -- a key the mask hides, whose value is never read into a sum, and a query nobody
+    reads), the dense kernels run under the layout's key mask, and the result's kept rows are packed again (xclip_pack_rows: +0 on filler rows,
+    what the varlen kernels write there).  The dense arrays are transients of this call; the tape keeps packed rows and the dense lse.
+    forward -> (o [R, inner], lse [batch, heads, n + 1]); backward -> dqkv [R, 3 inner]"""
+    spec, lay = c.spec, c.layout
+    n1 = lay.n + 1
+    qd = ops.unpack_rows(qkv, lay.cu, lay.pos, 0, n1)
+    if do is None:
+        od, lse = ops.attention_fwd(qd, c.mask, spec.heads, spec.scale, False, spec.head_slot)
+        return ops.pack_rows(od, lay.cu, lay.pos, 0), lse
+    dqd = ops.attention_bwd(qd, c.mask, ops.unpack_rows(o, lay.cu, lay.pos, 0, n1), ops.unpack_rows(do, lay.cu, lay.pos, 0, n1), lse,
+                            spec.heads, spec.scale, False, spec.head_slot)
+    return ops.pack_rows(dqd, lay.cu, lay.pos, 0)
 
 
 def _attn_forward(h: Tensor, W: LayerWeights, c: _Pass, seed: int):
@@ -208,6 +235,9 @@ def _attn_forward(h: Tensor, W: LayerWeights, c: _Pass, seed: int):
     if c.layout is not None:                                   # samples of different lengths, end to end: no mask, no dropout (text_encode_packed)
         if spec.rotary is not None:                            # q, k, v rotated by the position the row had in its sample, not by its packed index  :221-223
             ops.rotary_pos_(qkv, c.layout.pos, spec.rotary, head_dim=spec.head_slot)
+        if c.mask is not None:                                 # (the dense kernels on the rows put back by position: see _Pass)
+            o, lse = _attn_dense_on_packed(c, qkv)
+            return qkv, o, lse
         fwd = ops.attention_varlen_causal_fwd if spec.causal else ops.attention_varlen_fwd      # (causal: key j <= query i by packed row)
         o, lse = fwd(qkv, c.layout.cu, c.layout.max_len, spec.heads, spec.scale, spec.head_slot)
         return qkv, o, lse
@@ -266,6 +296,8 @@ def _ffn_backward(dx2: Tensor, t: LayerTape, W: LayerWeights, need: LayerWeights
 def _attn_backward(do: Tensor, t: LayerTape, c: _Pass, seed: int) -> Tensor:
     """the dense attention: gradient w.r.t. its output [M, inner] -> gradient w.r.t. the packed rotated qkv [M, 3 inner]"""
     spec, B, n, inner = c.spec, c.B, c.n, c.spec.inner
+    if c.layout is not None and c.mask is not None:
+        return _attn_dense_on_packed(c, t.qkv, t.o, do, t.lse)
     if c.layout is not None:
         bwd = ops.attention_varlen_causal_bwd if spec.causal else ops.attention_varlen_bwd
         return bwd(t.qkv, c.layout.cu, c.layout.max_len, t.o, do, t.lse, spec.heads, spec.scale, spec.head_slot)
@@ -453,16 +485,26 @@ def can_pool(spec: StackSpec) -> bool:
     return spec.depth >= 1 and spec.attn_dropout == 0.0 and spec.ff_dropout == 0.0
 
 
+def _packed_key_mask(layout, pool_row, spec: StackSpec) -> Tensor:
+    """bool [batch, n + 1]: the positions a layout keeps -- the key mask the dense tower runs the same batch under (index arithmetic only)"""
+    assert layout is not None and layout.has_cls and not spec.causal and pool_row is None, "dense_attention: a CLS-token layout, every row wanted"
+    return (layout.row_of() >= 0).contiguous()
+
+
 def stack_forward(x0: Tensor, B: int, n: int, spec: StackSpec, params: Sequence[Tensor], mask: Optional[Tensor],
-                  out: Optional[Tensor] = None, out_group: int = 0, keep_tape: bool = True, pool_row: Optional[int] = None, layout=None):
+                  out: Optional[Tensor] = None, out_group: int = 0, keep_tape: bool = True, pool_row: Optional[int] = None, layout=None,
+                  dense_attention: bool = False):
     """x0 [B*n, D] -> norm_out(...) [B*n, D] (or written into `out`, see ops.layernorm_fwd) and the backward tape.
     pool_row = r: only token row r of every sample is wanted -> [B, D] (the last layer's row-wise part runs on those rows alone).
     layout (packing.TextLayout): x0 is [R, D], the kept rows end to end (_Pass); every layer runs on all R rows -- with pool_row = 0 (the first
-    row of every sample, its CLS row) the last layer's row-wise part runs on those B rows (_layer_forward_pooled_packed) -> [B, D]"""
+    row of every sample, its CLS row) the last layer's row-wise part runs on those B rows (_layer_forward_pooled_packed) -> [B, D].
+    dense_attention (with a layout that has CLS rows, no pooled layer): every layer's attention runs through the dense kernels on the rows put
+    back by position (_attn_dense_on_packed); pass the same flag to stack_backward"""
     assert len(params) == 2 + LAYER_PARAMS * spec.depth
     assert pool_row is None or (can_pool(spec) and out is None and 0 <= pool_row < n)
     assert layout is None or (pool_row in (None, 0) and mask is None and out is None and x0.shape[0] == layout.R)
     assert layout is None or spec.causal == layout.ends_at_eos, "a causal stack takes a layout that ends at the EOS row, and only it"
+    mask = _packed_key_mask(layout, pool_row, spec) if dense_attention else mask
     x, m_in, r_in = ops.layernorm_fwd(x0, params[0])
     # dropout: one 64-bit seed per pass from torch's CPU generator (no device sync; torch.manual_seed makes it reproducible); layer l
     # uses seed + 2 l (attention) and seed + 2 l + 1 (feed-forward); the backward and a checkpointed re-run regenerate the same masks
@@ -481,9 +523,10 @@ def stack_forward(x0: Tensor, B: int, n: int, spec: StackSpec, params: Sequence[
 
 
 def stack_backward(dy: Tensor, tape, B: int, n: int, spec: StackSpec, params: Sequence[Tensor], mask: Optional[Tensor], need: Sequence[bool],
-                   layout=None):
+                   layout=None, dense_attention: bool = False):
     """dy [B*n, D] contiguous ([B, D] for a pooled forward; [R, D] with the forward's `layout`) -> (dx0, grads aligned with `params` (None where not needed))"""
     x0, m_in, r_in, layers, x_last, m_out, r_out, seed0, pool_row = tape
+    mask = _packed_key_mask(layout, pool_row, spec) if dense_attention else mask
     gg = _GainGrads(params, (True,) + spec.depth * IS_GAIN + (True,))
     grads: List[Optional[Tensor]] = [None] * len(params)
     sg, c = _SideGemm(dy.device), _Pass(spec, B, n, mask, layout)
@@ -636,16 +679,24 @@ def text_encode(tokens: Tensor, mask: Optional[Tensor], E: Tensor, P: Optional[T
 class _PackedTextEncodeFn(torch.autograd.Function):
     """the text encoder on the kept rows alone (packing.TextLayout) -> the CLS row of every sample [b, D].  Padded rows are never embedded,
     normalised, multiplied or attended from, forward or backward; no [b (n + 1), D] array is allocated on this path.
-    pool_last: the stack is asked for the CLS rows (stack_forward `pool_row = 0`): its last layer runs everything behind the attention on them alone"""
+    pool_last: the stack is asked for the CLS rows (stack_forward `pool_row = 0`): its last layer runs everything behind the attention on them alone
+    pool_last = None (text_encode_packed(rows=True)): the stack's whole [R, D] output is the result, for the heads that read token rows (the
+    fine-grained head, the MLM head, return_encodings); dy [R, D] enters stack_backward as it is"""
 
     @staticmethod
-    def forward(ctx, spec: StackSpec, layout, grad_mode: bool, pool_last: bool, E: Tensor, P: Optional[Tensor], cls: Tensor, *stack: Tensor):
+    def forward(ctx, spec: StackSpec, layout, grad_mode: bool, pool_last: Optional[bool], E: Tensor, P: Optional[Tensor], cls: Tensor, *stack: Tensor):
         keep = grad_mode and any(ctx.needs_input_grad)
         x0 = ops.text_embed_packed_fwd(layout.tok, layout.pos, E, P, cls)                # token_emb + pos, the cls rows   :320-331
-        y, tape = stack_forward(x0, layout.batch, layout.max_len, spec, stack, None, keep_tape=keep, pool_row=0 if pool_last else None, layout=layout)
+        # every row wanted (rows=True): where the varlen attention would take its plain form (fp32, 128-wide slots, a sample beyond the
+        # head-resident limit) the attention runs through the dense kernels instead, so that the kept rows are the dense tower's bit for bit
+        dense_attn = pool_last is None and not varlen_is_head_resident(E.dtype, spec.head_slot, layout.max_len)
+        y, tape = stack_forward(x0, layout.batch, layout.max_len, spec, stack, None, keep_tape=keep, pool_row=0 if pool_last else None, layout=layout,
+                                dense_attention=dense_attn)
         ctx.save_for_backward(*stack)
-        ctx.spec, ctx.layout, ctx.tape, ctx.pool_last = spec, layout, tape, pool_last
+        ctx.spec, ctx.layout, ctx.tape, ctx.pool_last, ctx.dense_attn = spec, layout, tape, pool_last, dense_attn
         ctx.meta = (E.shape[0], E.shape[1], 0 if P is None else P.shape[0], E.dtype)
+        if pool_last is None:
+            return y                                                                     # every kept row (and the filler rows behind them)
         return y if pool_last else ops.gather_rows(y, pooled_rows(layout))               # enc_text[:, 0] (causal: of eos_to_front)  :708
 
     @staticmethod
@@ -654,13 +705,14 @@ class _PackedTextEncodeFn(torch.autograd.Function):
         vocab, D, npos, dtype = ctx.meta
         lay = ctx.layout
         need = ctx.needs_input_grad[4:]
-        dyr = _contig_grad(dy, (lay.batch, D), dtype, lay.cu.device)
-        if not ctx.pool_last:
+        dyr = _contig_grad(dy, (lay.R if ctx.pool_last is None else lay.batch, D), dtype, lay.cu.device)
+        if ctx.pool_last is False:
             # dy into the CLS rows of a zeroed [R, D]: as a gather, row r takes dy[s] where r = cu[s] and the appended zero row elsewhere
             src = torch.full((lay.R,), lay.batch, dtype=torch.int32, device=dyr.device)
             src[pooled_rows(lay).long()] = torch.arange(lay.batch, dtype=torch.int32, device=dyr.device)
             dyr = ops.gather_rows(torch.cat([dyr, dyr.new_zeros(1, D)], dim=0), src)
-        dx0, sgrads = stack_backward(dyr, _take_tape(ctx), lay.batch, lay.max_len, ctx.spec, ctx.saved_tensors, None, need[3:], layout=lay)
+        dx0, sgrads = stack_backward(dyr, _take_tape(ctx), lay.batch, lay.max_len, ctx.spec, ctx.saved_tensors, None, need[3:], layout=lay,
+                                     dense_attention=ctx.dense_attn)
         dE = dP = dcls = None
         if need[0] or need[1] or need[2]:
             tok_key, pos_key = lay.keys(vocab, npos)
@@ -672,11 +724,13 @@ class _PackedTextEncodeFn(torch.autograd.Function):
 
 
 def text_encode_packed(layout, E: Tensor, P: Optional[Tensor], cls: Optional[Tensor], stack: Sequence[Tensor], spec: StackSpec,
-                       pool_last: bool = False) -> Tensor:
+                       pool_last: bool = False, rows: bool = False) -> Tensor:
     """TextTransformer.forward (x_clip.py:317-338) followed by `[:, 0]` (x_clip.py:708) for a packed batch -> [b, D]: the same function of
     the same tokens as text_encode(..., mask, pool_row=0), computed on the kept rows only.  Every layer runs on all R rows; with pool_last the
     last one runs its attention as one query per (sample, head) and everything behind it on the b CLS rows (the packed twin of the dense
-    path's pooled last layer, with its rounding points: see _layer_forward_pooled)."""
+    path's pooled last layer, with its rounding points: see _layer_forward_pooled).
+    rows = True (CLIP.pack_text_tokens): -> [R, D], the stack's output on every packed row -- row r is what the dense tower computes at
+    (sample of r, layout.pos[r]); unpack_rows puts them back by position.  Never pools the last layer"""
     # the causal encoder: no CLS row, a causal mask, read at the first EOS token -- on a layout that ends every sample there (text_layout(eos_id=))
     eos = cls is None and spec.causal and layout.ends_at_eos and not layout.has_cls
     if cls is None and not eos:
@@ -693,7 +747,57 @@ def text_encode_packed(layout, E: Tensor, P: Optional[Tensor], cls: Optional[Ten
         raise IndexError(f"text length {layout.n} exceeds max_seq_len {P.shape[0]}")
     if layout.cu.device != E.device:
         layout = layout.to(E.device)
+    if rows:
+        if eos:
+            raise NotImplementedError("pack_text: rows=True (every token row) is defined for the CLS-token encoder, not the causal one")
+        return _PackedTextEncodeFn.apply(spec, layout, torch.is_grad_enabled(), None, E, P, cls, *stack)
     return _PackedTextEncodeFn.apply(spec, layout, torch.is_grad_enabled(), bool(pool_last) and can_pool(spec), E, P, cls, *stack)
+
+
+class _UnpackRowsFn(torch.autograd.Function):
+    """packed [R, D] -> dense [b, n_out, D] by (sample, position) (xclip_unpack_rows); the backward is the transpose, xclip_pack_rows"""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, layout, pos0: int, n_out: int):
+        ctx.layout, ctx.pos0 = layout, pos0
+        return ops.unpack_rows(x, layout.cu, layout.pos, pos0, n_out)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        return ops.pack_rows(dy, ctx.layout.cu, ctx.layout.pos, ctx.pos0), None, None, None
+
+
+class _PackRowsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x: Tensor, layout, pos0: int):
+        ctx.layout, ctx.pos0, ctx.n_out = layout, pos0, x.shape[1]
+        return ops.pack_rows(x, layout.cu, layout.pos, pos0)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        return ops.unpack_rows(dy, ctx.layout.cu, ctx.layout.pos, ctx.pos0, ctx.n_out), None, None
+
+
+def _rows_layout(x: Tensor, layout, rows_dim: int):
+    if layout.cu.device != x.device:
+        layout = layout.to(x.device)
+    if x.dim() != rows_dim or (rows_dim == 2 and x.shape[0] != layout.R) or (rows_dim == 3 and x.shape[0] != layout.batch):
+        raise ValueError(f"packed rows are [R = {layout.R}, D], dense rows [batch = {layout.batch}, n_out, D]; got {tuple(x.shape)}")
+    return layout
+
+
+def unpack_rows(x: Tensor, layout, pos0: int, n_out: int) -> Tensor:
+    """x [R, D] on the rows of `layout` (packing.TextLayout) -> [batch, n_out, D]: out[s, p - pos0] = the row of sample s at position p, +0
+    where the layout keeps none.  pos0 = 1, n_out = n: `enc_text[:, 1:]` (x_clip.py:704); pos0 = 0, n_out = n + 1: the whole encoding"""
+    return _UnpackRowsFn.apply(x, _rows_layout(x, layout, 2), int(pos0), int(n_out))
+
+
+def pack_rows(x: Tensor, layout, pos0: int) -> Tensor:
+    """x [batch, n_out, D] -> [R, D]: out[r] = x[sample of r, layout.pos[r] - pos0], +0 on the rows in front of pos0 and on filler rows --
+    unpack_rows' transpose"""
+    return _PackRowsFn.apply(x, _rows_layout(x, layout, 3), int(pos0))
 
 
 # ---- vision encoder -----------------------------------------------------------------------------------------------------------

@@ -21,12 +21,14 @@ Tensor = torch.Tensor
 
 
 class _MlmHeadFn(torch.autograd.Function):
-    """emb [b, n + 1, D] (token 0 = CLS), flat row indices of the masked positions, their labels -> mean cross-entropy (fp32)"""
+    """emb [b, n + 1, D] (token 0 = CLS), flat row indices of the masked positions, their labels -> mean cross-entropy (fp32).
+    emb [R, D] (the packed tower, CLIP.pack_text_tokens): the indices are packed rows (TextLayout.row_of) and the backward scatters into
+    [R, D] -- no dense [b (n + 1), D] array on that path"""
 
     @staticmethod
     def forward(ctx, emb: Tensor, rows: Tensor, labels: Tensor, W: Tensor, bias: Tensor):
         emb = ops._c(emb)
-        B, n1, D = emb.shape
+        shape, D = tuple(emb.shape), emb.shape[-1]
         V = W.shape[0]
         dt, dev = emb.dtype, emb.device
         v = ops.vec(dt)
@@ -40,19 +42,19 @@ class _MlmHeadFn(torch.autograd.Function):
         else:
             Wp, bp = Wc, bc
         nm = rows.numel()
-        x = ops.gather_rows(emb.view(B * n1, D), rows)         # [nm, D]
+        x = ops.gather_rows(emb.view(-1, D), rows)             # [nm, D]
         logits = ops.gemm(x, Wp, nm, Vp, D, bias=bp)           # to_logits                                   mlm.py:100
         acc = torch.zeros(1, dtype=torch.float32, device=dev)
         lse = ops.cross_entropy_fwd(logits, V, labels, acc)    # F.cross_entropy over the non-ignored rows   mlm.py:103-107
         ctx.save_for_backward(x, Wp, logits, lse, labels, rows)
-        ctx.meta = (B, n1, D, V, Vp, dt, W.dtype, bias.dtype)
+        ctx.meta = (shape, D, V, Vp, dt, W.dtype, bias.dtype)
         return (acc / nm).reshape(())
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dloss):
         x, Wp, logits, lse, labels, rows = ctx.saved_tensors
-        B, n1, D, V, Vp, dt, wdt, bdt = ctx.meta
+        shape, D, V, Vp, dt, wdt, bdt = ctx.meta
         nm = rows.numel()
         dev = x.device
         g = dloss.detach().float().reshape(1).contiguous()
@@ -60,9 +62,9 @@ class _MlmHeadFn(torch.autograd.Function):
         demb = dW = db = None
         if ctx.needs_input_grad[0]:
             dx = ops.gemm(dlog, Wp, nm, D, Vp, b_kmajor=True)
-            table = torch.zeros(B * n1, D, dtype=torch.float32, device=dev)
+            table = torch.zeros(math.prod(shape[:-1]), D, dtype=torch.float32, device=dev)
             ops.rows_scatter_add(dx, rows, table, None)
-            demb = ops.cast_from_f32(table, dt).view(B, n1, D)
+            demb = ops.cast_from_f32(table, dt).view(shape)
         if ctx.needs_input_grad[3]:
             dW = ops.gemm(dlog, x, Vp, D, nm, a_kmajor=True, b_kmajor=True)[:V].to(wdt)
         if ctx.needs_input_grad[4]:
@@ -132,15 +134,29 @@ class MLM(nn.Module):
         masked = masked.masked_fill(chosen & show_mask, self.mask_token_id)
         return masked, labels
 
-    def forward(self, seq, **kwargs):
+    def forward(self, seq, layout=None, **kwargs):
+        """layout (not a reference keyword; packing.TextLayout of `seq` under its key mask, CLIP.pack_text_tokens): the tower runs on the kept rows
+        of the MASKED ids (layout.with_tokens: a masked position is never a pad, so the kept pattern is the same) and returns them [R, dim];
+        the head gathers the chosen positions by packed row (layout.row_of)"""
         masked, labels = self.masked_override if self.masked_override is not None else self.draw(seq)
         masked, labels = masked.to(seq.device), labels.to(seq.device)
-        emb = self.transformer(masked, **kwargs)                              # [b, n + 1, dim], CLS first      mlm.py:97
         b, n = labels.shape
-        assert emb.dim() == 3 and emb.shape[1] == n + 1, 'the MLM head expects the text encoder to prepend one CLS token'
-        pos = (labels != self.pad_token_id).nonzero()                         # rows that F.cross_entropy does not ignore
+        chosen = labels != self.pad_token_id                                  # rows that F.cross_entropy does not ignore
+        if layout is not None:
+            layout = layout.to(seq.device)
+            emb = self.transformer(masked, layout=layout.with_tokens(masked), rows=True, **kwargs)     # [R, dim]
+            assert emb.dim() == 2 and emb.shape[0] == layout.R and layout.has_cls, 'the packed MLM pass returns the kept rows of a CLS-token encoder'
+            row_of = layout.row_of()[:, 1:]                                   # logits[:, 1:]: skip the CLS position
+            chosen = chosen & (row_of >= 0)                                   # (a position an explicit key mask drops has no row to read)
+        else:
+            emb = self.transformer(masked, **kwargs)                          # [b, n + 1, dim], CLS first      mlm.py:97
+            assert emb.dim() == 3 and emb.shape[1] == n + 1, 'the MLM head expects the text encoder to prepend one CLS token'
+        pos = chosen.nonzero()
         if pos.shape[0] == 0:
             return torch.full((), float('nan'), dtype=torch.float32, device=seq.device)   # mean over nothing, like the reference
-        rows = (pos[:, 0] * (n + 1) + 1 + pos[:, 1]).to(torch.int32).contiguous()          # logits[:, 1:]: skip the CLS position
+        if layout is not None:
+            rows = row_of[pos[:, 0], pos[:, 1]].contiguous()
+        else:
+            rows = (pos[:, 0] * (n + 1) + 1 + pos[:, 1]).to(torch.int32).contiguous()      # logits[:, 1:]: skip the CLS position
         picked = labels[pos[:, 0], pos[:, 1]].contiguous()
         return _MlmHeadFn.apply(emb, rows, picked, self.to_logits.weight, self.to_logits.bias)

@@ -1377,6 +1377,39 @@ def rows_add_at(dst: Tensor, idx: Tensor, src: Tensor) -> Tensor:
     return dst
 
 
+def _pack_rows_args(cu: Tensor, pos: Tensor, rows: int):
+    assert cu.dtype == torch.int32 and pos.dtype == torch.int32 and cu.dim() == 1 and pos.dim() == 1 and cu.numel() >= 1
+    assert cu.is_contiguous() and pos.is_contiguous() and pos.numel() == rows, "cu int32 [batch + 1], pos int32 [rows] (packing.TextLayout)"
+
+
+def unpack_rows(packed: Tensor, cu: Tensor, pos: Tensor, pos0: int, n_out: int) -> Tensor:
+    """packed [rows, D] (packing.TextLayout: cu int32 [batch + 1], pos int32 [rows]) -> dense [batch, n_out, D]: dense[s, p - pos0] = the packed
+    row of sample s at position p, +0 where the layout keeps no such row.  Every row of the result is written by the one launch"""
+    _dev_check(packed, cu, pos)
+    packed = _c(packed)
+    assert packed.dim() == 2
+    _pack_rows_args(cu, pos, packed.shape[0])
+    batch, D = cu.numel() - 1, packed.shape[1]
+    dense = torch.empty(batch, n_out, D, dtype=packed.dtype, device=packed.device)
+    _lib.check(_lib.lib().xclip_unpack_rows(packed.data_ptr(), cu.data_ptr(), pos.data_ptr(), dense.data_ptr(), packed.shape[0], batch, n_out, pos0, D,
+                                            dtype_code(packed), _stream(packed)), "xclip_unpack_rows")
+    return dense
+
+
+def pack_rows(dense: Tensor, cu: Tensor, pos: Tensor, pos0: int) -> Tensor:
+    """unpack_rows' transpose: dense [batch, n_out, D] -> packed [rows, D], packed[r] = dense[sample of r, pos[r] - pos0], +0 on the rows in front
+    of pos0 (the CLS rows when pos0 = 1) and on the filler rows behind cu[batch]"""
+    _dev_check(dense, cu, pos)
+    dense = _c(dense)
+    assert dense.dim() == 3 and dense.shape[0] == cu.numel() - 1
+    _pack_rows_args(cu, pos, pos.numel())
+    batch, n_out, D = dense.shape
+    packed = torch.empty(pos.numel(), D, dtype=dense.dtype, device=dense.device)
+    _lib.check(_lib.lib().xclip_pack_rows(dense.data_ptr(), cu.data_ptr(), pos.data_ptr(), packed.data_ptr(), pos.numel(), batch, n_out, pos0, D,
+                                          dtype_code(dense), _stream(dense)), "xclip_pack_rows")
+    return packed
+
+
 def cross_entropy_fwd(logits: Tensor, cols: int, labels: Tensor, loss_accum: Tensor) -> Tensor:
     """lse [rows] of logits[:, :cols]; *loss_accum += sum_r (lse[r] - logits[r, labels[r]])   (mlm.py:103-107)"""
     _dev_check(logits, labels, loss_accum)

@@ -65,6 +65,34 @@ class TextLayout:
         return (torch.where(is_cls, torch.full_like(self.tok, vocab), self.tok),
                 torch.where(is_cls, torch.full_like(self.tok, npos), self.pos.to(torch.int64) - 1))
 
+    def _flat(self) -> Tensor:
+        """int64 [kept]: sample * (n + has_cls) + pos of every owned row -- its place in the dense [B, n + has_cls] order.  Index arithmetic on
+        cu and pos alone: nothing is read back from the device"""
+        rows = torch.arange(self.kept, dtype=self.cu.dtype, device=self.cu.device)
+        sample = torch.searchsorted(self.cu[1:], rows, right=True)          # the largest s with cu[s] <= r
+        return sample * (self.n + int(self.has_cls)) + self.pos[:self.kept].to(torch.int64)
+
+    def with_tokens(self, tokens: Tensor) -> "TextLayout":
+        """the same layout with `tok` gathered from another int64 [B, n] id tensor whose kept pattern is this one's (the MLM pass: the masked ids
+        sit exactly where the original ones do, a masked position is never a pad).  cu, pos and every count are shared; no device read"""
+        if tokens.dtype != torch.int64 or tuple(tokens.shape) != (self.batch, self.n):
+            raise TypeError(f"with_tokens: int64 tokens [{self.batch}, {self.n}], got {tokens.dtype} {tuple(tokens.shape)}")
+        tokens = tokens.to(self.cu.device)
+        if self.has_cls:
+            tokens = torch.cat([tokens.new_zeros(self.batch, 1), tokens], dim=1)
+        tok = tokens.reshape(-1)[self._flat()]
+        if self.R > self.kept:
+            tok = torch.cat([tok, tok.new_zeros(self.R - self.kept)])
+        return TextLayout(self.cu, self.pos, tok.contiguous(), self.R, self.max_len, self.batch, self.n, self.has_cls, self.ends_at_eos,
+                          self.kept, self.row_multiple)
+
+    def row_of(self) -> Tensor:
+        """int32 [B, n + has_cls]: the packed row of every dense position, -1 where the position is dropped.  No device read"""
+        npos = self.n + int(self.has_cls)
+        out = torch.full((self.batch * npos,), -1, dtype=torch.int32, device=self.cu.device)
+        out[self._flat()] = torch.arange(self.kept, dtype=torch.int32, device=self.cu.device)
+        return out.view(self.batch, npos)
+
 
 def cat_layouts(layouts) -> TextLayout:
     """the layout of several padded batches stacked along the batch dimension (the text batch and its augmented views, x_clip.py:629-639)"""
