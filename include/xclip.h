@@ -20,7 +20,7 @@ extern "C" {
 #endif
 
 enum { XCLIP_F32 = 0, XCLIP_BF16 = 1 };
-#define XCLIP_ABI_VERSION 36
+#define XCLIP_ABI_VERSION 37
 
 int xclip_abi_version(void);
 const char* xclip_last_error(void);
@@ -109,10 +109,20 @@ int xclip_add(const void* a, const void* b, void* out, int64_t count, int dtype,
 
 /* table_accum[idx[r], :] += src[r, :] (fp32; NULL: skipped) and colsum_accum[:] += sum_r src[r, :] (fp32; NULL: skipped):
  * the gradients of the position table gathered by the kept-patch index and of the patch-embedding bias
- * (x_clip.py:358,382-385).  workspace (optional, xclip_rows_scatter_add_workspace_bytes): per-wave partial rows for the column sum. */
+ * (x_clip.py:358,382-385).  workspace (optional, xclip_rows_scatter_add_workspace_bytes): per-wave partial rows for the column sum.
+ * Rows up to 4096 elements; the column sum ALONE (idx == table_accum == NULL) takes rows of any width and then needs the workspace
+ * (it runs as xclip_colsum). */
 int64_t xclip_rows_scatter_add_workspace_bytes(int64_t rows, int64_t dim);
 int xclip_rows_scatter_add(const void* src, int64_t lds, const int32_t* idx, float* table_accum, float* colsum_accum,
                            int64_t rows, int64_t dim, void* workspace, int64_t workspace_bytes, int dtype, void* stream);
+
+/* colsum_accum[:] += sum_r src[r, :] (fp32) for src [rows, dim] with row stride lds, rows of ANY width: the bias gradient of the MLM
+ * vocabulary head (`to_logits`, mlm.py:100-107).  Per-wave fp32 partial rows in the workspace (required, xclip_colsum_workspace_bytes),
+ * folded in a fixed order; each column meets the accumulator in one addition -- no atomics between work-groups, the same bits on every call. */
+int64_t xclip_colsum_workspace_bytes(int64_t rows, int64_t dim);
+/* mlm.py:100-107 */
+int xclip_colsum(const void* src, int64_t lds, float* colsum_accum, int64_t rows, int64_t dim, void* workspace, int64_t workspace_bytes,
+                 int dtype, void* stream);
 
 /* table_accum[sorted_ids[e], :] += src[row(perm[e]), :], e in [0, count): `sorted_ids` ascending (int64), perm[e] = the flat
  * index entry e had before sorting, row(p) = (p / n_in) * n_out + p % n_in + row_off.  Equal ids are summed in registers and
@@ -427,6 +437,25 @@ int xclip_cross_entropy_fwd(const void* logits, int64_t ld, const int64_t* label
                             int dtype, void* stream);
 int xclip_cross_entropy_bwd(void* logits, int64_t ld, const int64_t* labels, const float* lse, const float* gmul, int64_t rows, int64_t cols,
                             int dtype, void* stream);
+/* The same head WITHOUT the logits matrix (kernels/vocabce.h): z = x W^T + bias is formed tile by tile on the contrastive head's tile
+ * loop and reduced where it is made.  x [rows, dim] (the gathered masked rows), W [vocab, dim] and bias [vocab] in the storage dtype,
+ * contiguous, W as it is (no padded copy); labels int64 [rows], each in [0, vocab).
+ * vocab_ce_fwd: lse[r] = log sum_c exp(z[r, c]) from the fp32 accumulators; *loss_accum += sum_r (lse[r] - z[r, labels[r]]), summed in
+ *   a fixed order (two calls give the same bits).  Nothing of size rows x vocab is written.
+ * vocab_ce_bwd: G[r, c] = (*gmul / rows) (exp(z[r, c] - lse[r]) - [c == labels[r]]) in the storage dtype, row stride ldg >= vocab
+ *   rounded up to the 16-byte chunk; the padding columns up to that chunk are +0.  dx = G W, dW = G^T x and db = xclip_colsum(G) are
+ *   the caller's.
+ * workspace: xclip_vocab_ce_workspace_bytes(rows, vocab) = 4 * (roundup(vocab, 256) + (2 * ceil(vocab / 64) + 2) * rows) bytes, 16-byte
+ *   aligned: the bias row as fp32 padded to whole tiles, a (max, sum) pair per row and 64-column slot, the label logits, the row
+ *   losses.  vocab_ce_bwd uses the first roundup(vocab, 256) floats of it.  rows == 0 returns 0; x, W, G 16-byte aligned; dim a whole
+ *   number of 16-byte chunks.  The caller owns every buffer; nothing allocates, nothing synchronises. */
+int64_t xclip_vocab_ce_workspace_bytes(int64_t rows, int64_t vocab);
+/* mlm.py:100-107 */
+int xclip_vocab_ce_fwd(const void* x, const void* W, const void* bias, const int64_t* labels, int64_t rows, int64_t vocab, int64_t dim,
+                       void* workspace, float* lse, float* loss_accum, int dtype, void* stream);
+/* mlm.py:100-107 */
+int xclip_vocab_ce_bwd(const void* x, const void* W, const void* bias, const int64_t* labels, const float* lse, const float* gmul,
+                       int64_t rows, int64_t vocab, int64_t dim, void* G, int64_t ldg, void* workspace, int dtype, void* stream);
 /* `downsample_image_embeds` (x_clip.py:560-568), first stage: the depthwise Conv2d(C, C, 4, stride 2, padding 1, groups C, no bias)
  * over the image tokens laid out as an h x h grid.  x [batch, h*h, C] token-major, w [C, 16] (= the Conv2d weight [C, 1, 4, 4]),
  * y [batch, (h/2)^2, C].  (The 1 x 1 Conv2d with bias that follows is xclip_gemm with a bias row.)  bwd: dx [batch, h*h, C] and

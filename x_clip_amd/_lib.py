@@ -43,6 +43,8 @@ _SIGNATURES = {
     "xclip_add": (c_int, [P, P, P, L, I, P]),
     "xclip_rows_scatter_add_workspace_bytes": (c_int64, [L, L]),
     "xclip_rows_scatter_add": (c_int, [P, L, P, P, P, L, L, P, L, I, P]),
+    "xclip_colsum_workspace_bytes": (c_int64, [L, L]),
+    "xclip_colsum": (c_int, [P, L, P, L, L, P, L, I, P]),
     "xclip_scatter_add_sorted": (c_int, [P, L, P, P, P, L, L, L, L, L, L, I, P]),
     "xclip_sort_ids_workspace_bytes": (L, [L]),
     "xclip_sort_ids": (c_int, [P, L, L, P, P, P, L, P]),
@@ -89,6 +91,9 @@ _SIGNATURES = {
     "xclip_pack_rows": (c_int, [P, P, P, P, L, L, L, L, L, I, P]),
     "xclip_cross_entropy_fwd": (c_int, [P, L, P, L, L, P, P, I, P]),
     "xclip_cross_entropy_bwd": (c_int, [P, L, P, P, P, L, L, I, P]),
+    "xclip_vocab_ce_workspace_bytes": (c_int64, [L, L]),
+    "xclip_vocab_ce_fwd": (c_int, [P, P, P, P, L, L, L, P, P, P, I, P]),
+    "xclip_vocab_ce_bwd": (c_int, [P, P, P, P, P, P, L, L, L, P, L, P, I, P]),
     "xclip_batchnorm_workspace_bytes": (c_int64, [L, L]),
     "xclip_batchnorm_fwd": (c_int, [P, P, P, P, P, P, P, P, F, F, I, I, L, L, P, L, I, P]),
     "xclip_batchnorm_bwd": (c_int, [P, P, P, P, P, P, P, P, P, I, I, L, L, P, L, I, P]),
@@ -121,7 +126,7 @@ _SIGNATURES = {
     "xclip_grad_accumulate": (c_int, [P, L, L, I, P, I, P]),
 }
 EXPORTS = tuple(_SIGNATURES)
-ABI_VERSION = 36
+ABI_VERSION = 37
 
 
 def _bind(path: str):

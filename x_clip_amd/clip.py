@@ -649,6 +649,17 @@ class CLIP(nn.Module):
             raise NotImplementedError(f"CLIP.pack_text_tokens is not available with {why}")
 
     @property
+    def fuse_mlm_head(self):
+        """the MLM vocabulary head without its logits matrix (MLM.fused_head; csrc/kernels/vocabce.h).  Off by default."""
+        return self.use_mlm and self.mlm.fused_head
+
+    @fuse_mlm_head.setter
+    def fuse_mlm_head(self, on):
+        if not self.use_mlm:
+            raise ValueError("CLIP.fuse_mlm_head is the vocabulary head of the masked-language-model loss: this model was built without use_mlm=True")
+        self.mlm.fused_head = bool(on)
+
+    @property
     def pack_text_row_multiple(self):
         return self._pack_text_row_multiple
 

@@ -317,6 +317,31 @@ __global__ __launch_bounds__(256) void rows_scatter_add_kernel(const T* __restri
     }
 }
 
+// the column sum alone for rows of ANY width (the MLM head's bias gradient over a vocabulary, mlm.py:100-107): a wave owns one strip of
+// 64 chunks (blockIdx.x) and walks the rows blockIdx.y * 4 + wave, + 4 gridDim.y, ... of it with ONE chunk of sums in registers --
+// rows_scatter_add_kernel holds the whole row in MAXC chunks per lane and stops at 4096 elements.  partial: [gridDim.y * 4, D] fp32,
+// one row per wave of a strip column (a wave without rows writes zeros: every element is defined); the caller folds them with
+// colsum_fold_kernel.  No atomics here.
+template <typename T>
+__global__ __launch_bounds__(256) void colsum_wide_kernel(const T* __restrict__ src, long lds_, long rows, int D,
+                                                          float* __restrict__ partial) {
+    constexpr int VEC = Elem<T>::VEC;
+    const int c = blockIdx.x * 64 + lane_id();
+    if (c >= D / VEC) return;
+    float acc[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
+    for (long r = (long)blockIdx.y * 4 + wave_id(); r < rows; r += (long)gridDim.y * 4) {
+        float v[VEC];
+        load_vec<T>(src + r * lds_ + (long)c * VEC, v);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) acc[k] += v[k];
+    }
+    float* out = partial + ((long)blockIdx.y * 4 + wave_id()) * D + (long)c * VEC;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) out[k] = acc[k];
+}
+
 // ---- sorted segmented scatter-add (token-embedding / position-table gradients) --------------------------------
 // table[ids[e], :] += src[row(perm[e]), :] for e in [0, count), where `ids` is SORTED ascending and perm[e] is the
 // original position of entry e; row(p) = (p / n_in) * n_out + p % n_in + row_off maps a flat token index to its row of

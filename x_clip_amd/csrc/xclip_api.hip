@@ -24,6 +24,7 @@
 #include "kernels/simrank.h"
 #include "kernels/simtopk.h"
 #include "kernels/sigloss.h"
+#include "kernels/vocabce.h"
 #include "kernels/sort.h"
 #include "kernels/tokens.h"
 #include "kernels/embed_packed.h"
@@ -781,6 +782,44 @@ int xclip_add(const void* a, const void* b, void* out, int64_t count, int dtype,
     return check_launch(__func__);
 }
 
+// ---- column sum for rows of any width (tokens.h colsum_wide_kernel) ----
+// work-groups of 4 waves over the rows: as many as there are rows to give every wave one, capped so that strips x row groups stays near
+// 2048 work-groups (and the partial rows at 256).  A strip is the 64 chunks a wave's lanes hold: 64 * vec columns.
+inline int64_t colsum_row_blocks(int64_t rows, int64_t dim, int vec) {
+    int64_t cap = 2048 / ((dim / vec + 63) / 64);
+    cap = cap < 1 ? 1 : (cap > 64 ? 64 : cap);
+    const int64_t want = (rows + 3) / 4;
+    return want < cap ? (want < 1 ? 1 : want) : cap;
+}
+static int colsum_wide(const char* fn, const void* src, int64_t lds, float* colsum_accum, int64_t rows, int64_t dim, void* workspace,
+                                    int64_t workspace_bytes, int dtype, hipStream_t st) {
+    const int vec = vec_of(dtype);
+    const int64_t rb = colsum_row_blocks(rows, dim, vec);
+    if (!(workspace != nullptr && workspace_bytes >= rb * 4 * dim * 4)) return fail(fn, "rows this wide need the workspace (xclip_colsum_workspace_bytes)");
+    if (!(dim < (1LL << 31))) return fail(fn, "row too wide for 32-bit column indices");
+    dim3 grid((unsigned)((dim / vec + 63) / 64), (unsigned)rb), block(256);
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((colsum_wide_kernel<T>), grid, block, 0, st, (const T*)src, (long)lds, (long)rows, (int)dim, (float*)workspace);
+    });
+    // ONE slice: a column's partial rows are summed in a fixed order and meet the accumulator in one addition
+    hipLaunchKernelGGL(colsum_fold_kernel, dim3((unsigned)((dim + 63) / 64), 1), dim3(256), 1024, st, (const float*)workspace, (long)dim,
+                       colsum_accum, (int)(rb * 4), (int)dim);
+    return check_launch(fn);
+}
+
+// (no dtype here: the bf16 strip is the wider one, so its row-group count is the larger of the two)
+int64_t xclip_colsum_workspace_bytes(int64_t rows, int64_t dim) { return colsum_row_blocks(rows, dim, 8) * 4 * dim * 4; }
+
+int xclip_colsum(const void* src, int64_t lds, float* colsum_accum, int64_t rows, int64_t dim, void* workspace, int64_t workspace_bytes,
+                 int dtype, void* stream) {
+    XC_REQUIRE(dtype_ok(dtype), "bad dtype");
+    const int vec = vec_of(dtype);
+    XC_REQUIRE(rows >= 0 && dim > 0 && dim % vec == 0 && lds % vec == 0 && lds >= dim, "dim / lds must be chunk multiples covering a row");
+    if (rows == 0) return 0;                                  // (an empty tensor has a null data pointer)
+    XC_REQUIRE(src != nullptr && colsum_accum != nullptr && aligned16(src), "null or misaligned pointer");
+    return colsum_wide(__func__, src, lds, colsum_accum, rows, dim, workspace, workspace_bytes, dtype, (hipStream_t)stream);
+}
+
 int64_t xclip_rows_scatter_add_workspace_bytes(int64_t rows, int64_t dim) {
     int64_t blocks = (rows + 3) / 4;
     if (blocks > 256) blocks = 256;
@@ -796,6 +835,9 @@ int xclip_rows_scatter_add(const void* src, int64_t lds, const int32_t* idx, flo
     XC_REQUIRE(table_accum == nullptr || idx != nullptr, "table_accum needs idx");
     if (rows == 0) return 0;
     const int cpl = chunks_per_lane(dim, vec);
+    // the column sum alone over rows wider than the dispatch below takes (the MLM head's bias gradient over a vocabulary): colsum_wide_kernel
+    if (idx == nullptr && table_accum == nullptr && colsum_accum != nullptr && cpl > 4096 / 64 / vec)
+        return colsum_wide(__func__, src, lds, colsum_accum, rows, dim, workspace, workspace_bytes, dtype, (hipStream_t)stream);
     int64_t blocks = (rows + 3) / 4;
     if (blocks > 256) blocks = 256;
     // column sums go through per-wave partial rows + a fold (thousands of waves adding into the same `dim` floats serialise)
@@ -1696,6 +1738,67 @@ int xclip_sigloss_grad(const void* Q, const void* K, int64_t nq, int64_t nk, int
         sim_launch_g<SigParams, sig5_grad_kernel<true>, sig5_grad_kernel<false>, sig5_grad_edge_kernel>(p, p.s, st);
     else
         sim_launch_general<SigParams, sig_grad_kernel<bf16_t>, sig_grad_kernel<float>>(p, p.s, dtype, st);
+    return check_launch(__func__);
+}
+
+// ---- fused MLM vocabulary head on the head's tile loop (kernels/vocabce.h; mlm.py:100-107) ----
+// workspace (floats): the bias row as fp32 padded to whole 256-column tiles | part_m, part_l [slots][rows] | zlab [rows] | rowloss [rows]
+inline int64_t vocab_bias_cols(int64_t vocab) { return (vocab + 255) / 256 * 256; }
+int64_t xclip_vocab_ce_workspace_bytes(int64_t rows, int64_t vocab) {
+    return (vocab_bias_cols(vocab) + (2 * ((vocab + 63) / 64) + 2) * rows) * 4;
+}
+static void vocab_bias(const void* bias, float* out, int64_t vocab, int dtype, hipStream_t st) {
+    const int64_t padded = vocab_bias_cols(vocab);
+    by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((vocab_bias_kernel<T>), dim3((unsigned)(padded / 256)), dim3(256), 0, st, (const T*)bias, out, (int)vocab, (int)padded);
+    });
+}
+
+int xclip_vocab_ce_fwd(const void* x, const void* W, const void* bias, const int64_t* labels, int64_t rows, int64_t vocab, int64_t dim,
+                       void* workspace, float* lse, float* loss_accum, int dtype, void* stream) {
+    XC_REQUIRE(dtype_ok(dtype), "bad dtype");
+    XC_REQUIRE(rows >= 0, "bad shape");
+    if (rows == 0) return 0;                                  // (an empty tensor has a null data pointer)
+    XC_SIM_REQUIRE(sim_bad_args(x, W, rows, vocab, dim, 0, dtype));
+    XC_REQUIRE(bias && labels && lse && loss_accum && workspace && aligned16(workspace), "null or misaligned pointer");
+    VocabParams p;
+    memset(&p, 0, sizeof(p));
+    p.s = sim_params(x, W, rows, vocab, dim, 1.0f, nullptr, 0, 0);
+    const int64_t slots = (vocab + 63) / 64;
+    float* ws = (float*)workspace;
+    p.bias = ws;
+    p.s.part_m = ws + vocab_bias_cols(vocab); p.s.part_l = p.s.part_m + slots * rows; p.s.pos = p.s.part_l + slots * rows;
+    float* rowloss = p.s.pos + rows;
+    p.label = (const long long*)labels;
+    hipStream_t st = (hipStream_t)stream;
+    vocab_bias(bias, ws, vocab, dtype, st);
+    sim_launch<VocabParams, vocab5_lse_kernel, vocab_lse_partial_kernel<bf16_t>, vocab_lse_partial_kernel<float>>(p, p.s, dtype, st);
+    hipLaunchKernelGGL(vocab_combine_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(1024), 2 * 16 * 64 * 4, st, (const float*)p.s.part_m,
+                       (const float*)p.s.part_l, (const float*)p.s.pos, lse, rowloss, (int)rows, (int)slots);
+    hipLaunchKernelGGL(sigloss_total_kernel, dim3(1), dim3(1024), 16 * 4, st, (const float*)rowloss, loss_accum, (int)rows, 1.0f);
+    return check_launch(__func__);
+}
+
+int xclip_vocab_ce_bwd(const void* x, const void* W, const void* bias, const int64_t* labels, const float* lse, const float* gmul,
+                       int64_t rows, int64_t vocab, int64_t dim, void* G, int64_t ldg, void* workspace, int dtype, void* stream) {
+    XC_REQUIRE(dtype_ok(dtype), "bad dtype");
+    XC_REQUIRE(rows >= 0, "bad shape");
+    if (rows == 0) return 0;                                  // (an empty tensor has a null data pointer)
+    XC_SIM_REQUIRE(sim_bad_args(x, W, rows, vocab, dim, 0, dtype));
+    XC_SIM_REQUIRE(sim_bad_g(G, ldg, rows, vocab, dim, dtype));
+    XC_REQUIRE(bias && labels && lse && gmul && workspace && aligned16(workspace), "null or misaligned pointer");
+    VocabParams p;
+    memset(&p, 0, sizeof(p));
+    p.s = sim_params(x, W, rows, vocab, dim, 1.0f, nullptr, 0, 0);
+    p.s.lse_q = lse; p.s.gmul = gmul; p.s.G = G; p.s.ldg = ldg;
+    p.bias = (const float*)workspace;
+    p.label = (const long long*)labels;
+    hipStream_t st = (hipStream_t)stream;
+    vocab_bias(bias, (float*)workspace, vocab, dtype, st);
+    if (use_sim3(rows, vocab, dim, dtype))
+        sim_launch_g<VocabParams, vocab5_grad_kernel<true>, vocab5_grad_kernel<false>, vocab5_grad_edge_kernel>(p, p.s, st);
+    else
+        sim_launch_general<VocabParams, vocab_grad_kernel<bf16_t>, vocab_grad_kernel<float>>(p, p.s, dtype, st);
     return check_launch(__func__);
 }
 

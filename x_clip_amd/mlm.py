@@ -74,6 +74,58 @@ class _MlmHeadFn(torch.autograd.Function):
         return demb, None, None, dW, db
 
 
+class _MlmFusedHeadFn(torch.autograd.Function):
+    """_MlmHeadFn without the logits matrix (MLM.fused_head; csrc/kernels/vocabce.h): the same arguments, dense or packed.  The forward
+    reduces z = x W^T + bias to lse and the label logit on the contrastive head's tile loop; the backward recomputes z and writes
+    G = dloss / nm (softmax - onehot) once.  W is used as it is (no padded copy); nothing with nm * V elements is saved."""
+
+    @staticmethod
+    def forward(ctx, emb: Tensor, rows: Tensor, labels: Tensor, W: Tensor, bias: Tensor):
+        emb = ops._c(emb)
+        shape, D = tuple(emb.shape), emb.shape[-1]
+        dt, dev = emb.dtype, emb.device
+        nm = rows.numel()
+        x = ops.gather_rows(emb.view(-1, D), rows)             # [nm, D]
+        acc = torch.zeros(1, dtype=torch.float32, device=dev)
+        lse = ops.vocab_ce_fwd(x, ops._c(W).to(dt), ops._c(bias).to(dt), labels, acc)    # to_logits + F.cross_entropy    mlm.py:100-107
+        ctx.save_for_backward(x, W, bias, lse, labels, rows)
+        ctx.meta = (shape, D, dt)
+        return (acc / nm).reshape(())
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dloss):
+        x, W, bias, lse, labels, rows = ctx.saved_tensors
+        shape, D, dt = ctx.meta
+        nm, V = rows.numel(), W.shape[0]
+        dev = x.device
+        g = dloss.detach().float().reshape(1).contiguous()
+        Wc = ops._c(W).to(dt)
+        G = ops.vocab_ce_bwd(x, Wc, ops._c(bias).to(dt), labels, lse, g)     # [nm, Vp], padding columns zero
+        Vp = G.shape[1]
+        demb = dW = db = None
+        if ctx.needs_input_grad[0]:
+            dx = ops.gemm(G, Wc if Vp == V else _pad_rows(Wc, Vp), nm, D, Vp, b_kmajor=True)
+            table = torch.zeros(math.prod(shape[:-1]), D, dtype=torch.float32, device=dev)
+            ops.rows_scatter_add(dx, rows, table, None)
+            demb = ops.cast_from_f32(table, dt).view(shape)
+        if ctx.needs_input_grad[3]:
+            dW = ops.gemm(G, x, Vp, D, nm, a_kmajor=True, b_kmajor=True)[:V].to(W.dtype)
+        if ctx.needs_input_grad[4]:
+            acc = torch.zeros(Vp, dtype=torch.float32, device=dev)
+            ops.colsum(G, acc)
+            db = acc[:V].to(bias.dtype)
+        return demb, None, None, dW, db
+
+
+def _pad_rows(W: Tensor, Vp: int) -> Tensor:
+    """W with zero rows up to Vp, for dx = G W over a vocabulary that is no whole number of 16-byte chunks: the GEMM's K runs over G's
+    padding columns too (the one padded copy the fused head still makes, in the backward only; 10,000 and 49,408 need none)"""
+    Wp = torch.zeros(Vp, W.shape[1], dtype=W.dtype, device=W.device)
+    Wp[:W.shape[0]].copy_(W)
+    return Wp
+
+
 def _any_of(t: Tensor, ids) -> Tensor:
     hit = torch.zeros_like(t, dtype=torch.bool)
     for i in ids:
@@ -115,6 +167,7 @@ class MLM(nn.Module):
         self.mask_ignore_token_ids = set([*mask_ignore_token_ids, pad_token_id])
         self.to_logits = nn.Linear(dim, num_tokens)
         self.masked_override: Optional[Tuple[Tensor, Tensor]] = None   # parity harness: (masked_seq, labels) instead of the random draw
+        self.fused_head = False                                        # the vocabulary head without its logits matrix (_MlmFusedHeadFn; CLIP.fuse_mlm_head)
 
     def draw(self, seq: Tensor) -> Tuple[Tensor, Tensor]:
         """(masked_seq, labels): mlm.py:70-94 -- special / pad tokens are never chosen; labels hold the original id at the chosen
@@ -159,4 +212,5 @@ class MLM(nn.Module):
         else:
             rows = (pos[:, 0] * (n + 1) + 1 + pos[:, 1]).to(torch.int32).contiguous()      # logits[:, 1:]: skip the CLS position
         picked = labels[pos[:, 0], pos[:, 1]].contiguous()
-        return _MlmHeadFn.apply(emb, rows, picked, self.to_logits.weight, self.to_logits.bias)
+        head = _MlmFusedHeadFn if self.fused_head else _MlmHeadFn
+        return head.apply(emb, rows, picked, self.to_logits.weight, self.to_logits.bias)

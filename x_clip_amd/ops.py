@@ -1430,6 +1430,66 @@ def cross_entropy_bwd_(logits: Tensor, cols: int, labels: Tensor, lse: Tensor, g
     return logits
 
 
+def _vocab_args(x: Tensor, W: Tensor, bias: Tensor, labels: Tensor):
+    assert x.dim() == 2 and W.dim() == 2 and x.shape[1] == W.shape[1] and x.dtype == W.dtype == bias.dtype
+    assert x.is_contiguous() and W.is_contiguous() and bias.is_contiguous() and bias.numel() == W.shape[0]
+    assert labels.dtype == torch.int64 and labels.is_contiguous() and labels.numel() == x.shape[0]
+    return x.shape[0], W.shape[0], x.shape[1]
+
+
+def vocab_ce_fwd(x: Tensor, W: Tensor, bias: Tensor, labels: Tensor, loss_accum: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """the MLM head without its logits (mlm.py:100-107): lse [rows] fp32 of z = x W^T + bias, x [rows, D], W [V, D] as it is, bias [V];
+    *loss_accum += sum_r (lse[r] - z[r, labels[r]]) in a fixed order.  Nothing of size rows x V is written.  `out`: an fp32 [rows]
+    tensor to receive lse."""
+    _dev_check(x, W, bias, labels, loss_accum, out)
+    rows, V, D = _vocab_args(x, W, bias, labels)
+    assert loss_accum.dtype == torch.float32 and loss_accum.numel() == 1
+    lse = torch.empty(rows, dtype=torch.float32, device=x.device) if out is None else out
+    assert lse.dtype == torch.float32 and lse.shape == (rows,) and lse.is_contiguous()
+    L = _lib.lib()
+    ws = workspace(x.device, L.xclip_vocab_ce_workspace_bytes(rows, V))
+    probe = _probe(x)
+    ev0 = probe.begin(x) if probe is not None else None
+    _lib.check(L.xclip_vocab_ce_fwd(x.data_ptr(), W.data_ptr(), bias.data_ptr(), labels.data_ptr(), rows, V, D, _ptr(ws), lse.data_ptr(),
+                                    loss_accum.data_ptr(), dtype_code(x), _stream(x)), "xclip_vocab_ce_fwd")
+    if probe is not None:
+        probe.end(x, ev0, "head", 2.0 * rows * V * D, (rows + V) * D * x.element_size(), "vocab_fwd")
+    return lse
+
+
+def vocab_ce_bwd(x: Tensor, W: Tensor, bias: Tensor, labels: Tensor, lse: Tensor, gmul: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """-> G [rows, V rounded up to the chunk] in x.dtype, G = (gmul / rows) (softmax(z) - onehot(labels)) with z recomputed from x, W and
+    bias; the padding columns are +0.  `out`: a [rows, >= roundup(V)] view (unit inner stride) to write into."""
+    _dev_check(x, W, bias, labels, lse, gmul, out)
+    rows, V, D = _vocab_args(x, W, bias, labels)
+    assert lse.dtype == torch.float32 and lse.shape == (rows,) and lse.is_contiguous()
+    G, ldg = _g_out(x, V, out, gmul)
+    assert gmul is not None
+    if rows == 0:
+        return G
+    L = _lib.lib()
+    ws = workspace(x.device, L.xclip_vocab_ce_workspace_bytes(rows, V))
+    probe = _probe(x)
+    ev0 = probe.begin(x) if probe is not None else None
+    _lib.check(L.xclip_vocab_ce_bwd(x.data_ptr(), W.data_ptr(), bias.data_ptr(), labels.data_ptr(), lse.data_ptr(), gmul.data_ptr(), rows, V, D,
+                                    G.data_ptr(), G.stride(0), ws.data_ptr(), dtype_code(x), _stream(x)), "xclip_vocab_ce_bwd")
+    if probe is not None:
+        probe.end(x, ev0, "head", 2.0 * rows * V * D, (rows + V) * D * x.element_size() + rows * ldg * x.element_size(), "vocab_grad")
+    return G
+
+
+def colsum(src: Tensor, accum: Tensor):
+    """accum [dim] (fp32) += src.sum(0) for src [rows, dim] of any width (unit inner stride), summed in a fixed order"""
+    _dev_check(src, accum)
+    assert src.dim() == 2 and src.stride(1) == 1
+    rows, dim = src.shape
+    assert accum.dtype == torch.float32 and accum.is_contiguous() and accum.numel() == dim
+    L = _lib.lib()
+    ws = workspace(src.device, L.xclip_colsum_workspace_bytes(rows, dim))
+    _lib.check(L.xclip_colsum(src.data_ptr(), src.stride(0), accum.data_ptr(), rows, dim, _ptr(ws), 0 if ws is None else ws.numel(),
+                              dtype_code(src), _stream(src)), "xclip_colsum")
+
+
 def layernorm_chain_fwd(p: Tensor, g1: Tensor, res: Tensor, g2: Tensor):
     """x1 = LN(p) g1 + res, h2 = LN(x1) g2 in one pass (x_clip.py:245,288-289 + :126) -> (x1, mean1, rstd1, h2, mean2, rstd2)"""
     _dev_check(p, g1, res, g2)
