@@ -20,7 +20,7 @@ extern "C" {
 #endif
 
 enum { XCLIP_F32 = 0, XCLIP_BF16 = 1 };
-#define XCLIP_ABI_VERSION 37
+#define XCLIP_ABI_VERSION 38
 
 int xclip_abi_version(void);
 const char* xclip_last_error(void);
@@ -564,6 +564,32 @@ int xclip_adamw_ema_step(const void* table, int64_t chunk0, int64_t count, int p
                          float* master, const void* state_block, int32_t* step_base, double lr, double beta1, double beta2, double eps,
                          double weight_decay, float* ema, double ema_decay, int ema_warmup, void* stream);
 int xclip_grad_accumulate(const void* table, int64_t chunk0, int64_t count, int g_dtype, float* acc, int materialise, void* stream);
+/* Layer-wise trust ratio (LAMB) and parameter bounds (ABI 38; FusedAdamW param-group keys `trust_ratio` / `bounds`).  They replace what a
+ * user would write after torch.optim.AdamW.step: timm / apex `Lamb.step` (a per-tensor `w.norm() / update.norm()` chain of foreach
+ * launches) and the `logit_scale.clamp_(lo, hi)` of the CLIP recipes, which on a bf16 model reaches only the rounded copy of the weight.
+ * Same table, state block, step_base and flat arrays as adamw_step; every entry returns at once when found_nonfinite is set.
+ *   lamb_norm (replaces the two `norm()` reductions per tensor of Lamb.step): chunks [chunk0, chunk0 + count) of (p_dtype, g_dtype) with one
+ *     group's betas / eps / weight_decay.  Per element g = clip_coef g; m' = b1 m + (1 - b1) g; v' = b2 v + (1 - b2) g^2;
+ *     u = (m' / (1 - b1^t)) / (sqrt(v' / (1 - b2^t)) + eps) + weight_decay w, t as adamw_step forms it (step_base is read, not written).
+ *     pairs[2 c] = sum w^2, pairs[2 c + 1] = sum u^2 over chunk c (fp32, fixed order, no atomics).  Nothing else is written.
+ *   lamb_fold (replaces the division of the two norms, per tensor on the host side of Lamb.step): for every record of the range with the
+ *     first-chunk flag, the pairs of that parameter's records (adjacent, inside the range) are added in record order in double and
+ *     ratio[parameter] = sqrt(sum w^2) / sqrt(sum u^2), 1 when either sum is 0.  ratio: fp32 [parameters]; other entries are not touched.
+ *   optim_update (replaces Lamb.step's `p.add_(update, alpha=-lr * trust_ratio)` and the recipes' `clamp_` after the step): adamw_step /
+ *     adamw_ema_step for a group with a trust ratio and / or bounds.  ratio != NULL: m, v become m', v' above and
+ *     w -= (lr ratio[parameter]) u; ratio == NULL: adamw_step's update, bit for bit.  Then w = min(max(w, lo), hi) on the fp32 weight
+ *     (lo = -inf / hi = +inf: no bound; both must be exactly representable in float and lo <= hi: round lo up and hi down to the
+ *     parameter's storage type before the call and the rounded bf16 parameter stays inside as well), then, ema != NULL, adamw_ema_step's
+ *     average of the clamped weight (ema == NULL: ema_decay / ema_warmup are ignored).  Records step_base as adamw_step does. */
+int xclip_lamb_norm(const void* table, int64_t chunk0, int64_t count, int p_dtype, int g_dtype, const float* exp_avg, const float* exp_avg_sq,
+                    const float* master, const void* state_block, const int32_t* step_base, double beta1, double beta2, double eps,
+                    double weight_decay, float* pairs, void* stream);
+int xclip_lamb_fold(const void* table, int64_t chunk0, int64_t count, const float* pairs, const void* state_block, float* ratio,
+                    void* stream);
+int xclip_optim_update(const void* table, int64_t chunk0, int64_t count, int p_dtype, int g_dtype, float* exp_avg, float* exp_avg_sq,
+                       float* master, const void* state_block, int32_t* step_base, double lr, double beta1, double beta2, double eps,
+                       double weight_decay, const float* ratio, double lo, double hi, float* ema, double ema_decay, int ema_warmup,
+                       void* stream);
 
 #ifdef __cplusplus
 }

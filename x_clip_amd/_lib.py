@@ -124,9 +124,13 @@ _SIGNATURES = {
     "xclip_adamw_step": (c_int, [P, L, L, I, I, P, P, P, P, P, D, D, D, D, D, P]),
     "xclip_adamw_ema_step": (c_int, [P, L, L, I, I, P, P, P, P, P, D, D, D, D, D, P, D, I, P]),
     "xclip_grad_accumulate": (c_int, [P, L, L, I, P, I, P]),
+    # ABI 38 -- trust ratio (LAMB) and bounds: replace timm / apex Lamb.step's per-tensor norms and scaled add, and the clamp_ after a step
+    "xclip_lamb_norm": (c_int, [P, L, L, I, I, P, P, P, P, P, D, D, D, D, P, P]),
+    "xclip_lamb_fold": (c_int, [P, L, L, P, P, P, P]),
+    "xclip_optim_update": (c_int, [P, L, L, I, I, P, P, P, P, P, D, D, D, D, D, P, D, D, P, D, I, P]),
 }
 EXPORTS = tuple(_SIGNATURES)
-ABI_VERSION = 37
+ABI_VERSION = 38
 
 
 def _bind(path: str):

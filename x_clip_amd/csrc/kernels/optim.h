@@ -13,9 +13,16 @@
 //   adamw_ema_kernel          the same pass with a weight EMA kept beside the moments (FusedAdamW(ema_decay=...)): + 8 bytes per parameter.
 //   grad_accum_kernel         gradients of several backward passes summed into a flat fp32 array and rounded once into `.grad`
 //                             (FusedAdamW.accumulate_begin / accumulate / accumulate_end; x_clip_amd/cached.py).
+//   lamb_norm_kernel          param groups with `trust_ratio` (LAMB): one work-group per chunk forms the update direction u from the
+//                             moments as they WILL be (nothing is stored) and writes the chunk's pair (sum w^2, sum u^2).
+//   lamb_fold_kernel          one thread per parameter: its chunks' pairs summed in chunk order, in double -> ratio[param] = |w| / |u|.
+//   optim_update_kernel       the update of a group with `trust_ratio` and / or `bounds`: AdamW's or LAMB's step, then the clamp of the
+//                             fp32 weight, then the EMA if on, one streaming pass; stores the moments.
 //
 // Algorithmic HBM traffic per parameter: bf16 2 (g, norm pass) + 2 (g) + 12 (m, v, master in) + 12 (out) + 2 (p out) = 30 bytes;
 // fp32 4 + 4 + 12 (m, v, p in) + 12 (out) = 32 bytes.  Everything is read once and written once: non-temporal hint, as in rows.h.
+// With `trust_ratio`: + lamb_norm_kernel's 2 (g) + 12 (m, v, master in) = 44 bytes bf16, + 4 + 12 = 48 bytes fp32 (its 8 bytes per
+// CHUNK out and the fold are noise); `bounds` alone move no byte more than adamw_kernel / adamw_ema_kernel.
 #pragma once
 #include "common.h"
 
@@ -320,6 +327,186 @@ __global__ __launch_bounds__(OPT_THREADS) void grad_accum_kernel(const OptChunk*
     for (int i = nvec * 8 + tid; i < c.n; i += OPT_THREADS) {  // scalar tail / unaligned chunk
         if (MATERIALISE) g[i] = from_f32<G>(a[i]);
         else a[i] += to_f32(g[i]);
+    }
+}
+
+// ---- layer-wise trust ratio (LAMB) and bounds --------------------------------------------------------------------------------------------
+// FusedAdamW param groups with `trust_ratio` and / or `bounds`.  LAMB as timm / apex state it, per parameter tensor:
+//   g = clip g;  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;  u = (m / bc1) / (sqrt(v / bc2) + eps) + wd w   (decay INSIDE u)
+//   r = |w| / |u| over the whole tensor (1 when either norm is 0);  w -= lr r u
+// r needs every element of the tensor before any of them moves, so the step is three launches: lamb_norm_kernel forms u per chunk
+// WITHOUT storing anything but the chunk's (sum w^2, sum u^2); lamb_fold_kernel adds a parameter's pairs in chunk order, in double
+// (its chunks are adjacent in the table, `first` marks where they start), into ratio[param]; optim_update_kernel<.., TRUST = true>
+// forms u again from the same inputs with the same function (lamb_elem) and stores m, v, w.  Both passes derive the parameter's own step
+// count t the same way; only the update pass records step_base, and it runs after the norm pass, so a parameter with its first gradient
+// gets one t in both.  `bounds`: lo <= w <= hi on the fp32 weight after the step (either kind), BEFORE the EMA reads it and before the
+// bf16 parameter is rounded from it; the host hands lo rounded up and hi rounded down to the parameter's storage type, so the rounded
+// parameter stays inside too; -inf / +inf: no bound.  Every kernel returns at once on a skipped step: ratio[] keeps its bits as well.
+struct UpdateArgs {                       // per param group, for the kernels below
+    AdamWArgs a;
+    float wd;                             // weight_decay (LAMB adds wd w to the update; AdamW uses a.decay)
+    float lo, hi;                         // bounds of the fp32 weight
+};
+
+// u of one element; m and v become the new moments (the norm pass drops them, the update pass stores them)
+XC_DEV float lamb_elem(float g, float w, float& m, float& v, const UpdateArgs& q, float clip, float rbc1, float rbc2_sqrt) {
+    g *= clip;
+    m = q.a.b1 * m + q.a.omb1 * g;
+    v = q.a.b2 * v + q.a.omb2 * (g * g);
+    return (m * rbc1) / (sqrtf(v) * rbc2_sqrt + q.a.eps) + q.wd * w;
+}
+
+XC_DEV float opt_clamp(float w, float lo, float hi) {          // (comparisons: a nan stays a nan, +-inf bounds change no bit)
+    w = w < lo ? lo : w;
+    return w > hi ? hi : w;
+}
+
+template <typename P, typename G, bool MASTER>
+__global__ __launch_bounds__(OPT_THREADS) void lamb_norm_kernel(const OptChunk* __restrict__ table, int chunk0,
+                                                                const float* __restrict__ exp_avg, const float* __restrict__ exp_avg_sq,
+                                                                const float* __restrict__ master, const OptBlock* __restrict__ blk,
+                                                                const int32_t* __restrict__ step_base, UpdateArgs q,
+                                                                float* __restrict__ pairs) {
+    XC_LDS_DYNAMIC(lds);                                       // 8 floats
+    float* red = reinterpret_cast<float*>(lds);
+    const OptBlock b = *blk;
+    if (b.found_nonfinite) return;                             // the step is skipped (uniform: nobody reaches the barrier)
+    const int chunk = chunk0 + (int)blockIdx.x;
+    const OptChunk c = table[chunk];
+    const int tid = threadIdx.x;
+    float aw[8], au[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) aw[j] = au[j] = 0.f;
+    if ((c.dtypes & 0xff) == OptDtype<P>::CODE && ((c.dtypes >> 8) & 0xff) == OptDtype<G>::CODE) {   // (else: reads nothing, r = 1)
+        int base = step_base[c.param];                         // (read only: optim_update_kernel records it)
+        if (base < 0) base = b.step - 1;
+        const int t = b.step - base;
+        const double bc1 = 1.0 - opt_ipow(q.a.beta1, t), bc2 = 1.0 - opt_ipow(q.a.beta2, t);
+        const float rbc1 = (float)(1.0 / bc1), rbc2_sqrt = (float)(1.0 / sqrt(bc2)), clip = b.clip_coef;
+        const G* g = reinterpret_cast<const G*>(c.g);
+        const float* m = exp_avg + c.state_off;
+        const float* v = exp_avg_sq + c.state_off;
+        const float* w = MASTER ? master + c.state_off : reinterpret_cast<const float*>(c.p);
+        const int nvec = (opt_aligned16(c.p) && opt_aligned16(c.g) && (c.state_off & 3) == 0) ? c.n / 8 : 0;
+        for (int i = tid; i < nvec; i += OPT_THREADS) {
+            const long o = (long)i * 8;
+            float gv[8], mv[8], vv[8], wv[8];
+            opt_load8<false>(g + o, gv);                       // (no hints: the update pass reads all four again)
+            opt_load8<false>(m + o, mv);
+            opt_load8<false>(v + o, vv);
+            opt_load8<false>(w + o, wv);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float u = lamb_elem(gv[j], wv[j], mv[j], vv[j], q, clip, rbc1, rbc2_sqrt);
+                aw[j] += wv[j] * wv[j];
+                au[j] += u * u;
+            }
+        }
+        for (int i = nvec * 8 + tid; i < c.n; i += OPT_THREADS) {   // scalar tail / unaligned chunk
+            float mi = m[i], vi = v[i];
+            const float wi = w[i], u = lamb_elem(to_f32(g[i]), wi, mi, vi, q, clip, rbc1, rbc2_sqrt);
+            aw[0] += wi * wi;
+            au[0] += u * u;
+        }
+    }
+    const float sw = wave_sum(((aw[0] + aw[1]) + (aw[2] + aw[3])) + ((aw[4] + aw[5]) + (aw[6] + aw[7])));
+    const float su = wave_sum(((au[0] + au[1]) + (au[2] + au[3])) + ((au[4] + au[5]) + (au[6] + au[7])));
+    if (lane_id() == 0) {
+        red[wave_id()] = sw;
+        red[4 + wave_id()] = su;
+    }
+    sync();
+    if (tid == 0) {
+        pairs[2 * (long)chunk] = (red[0] + red[1]) + (red[2] + red[3]);
+        pairs[2 * (long)chunk + 1] = (red[4] + red[5]) + (red[6] + red[7]);
+    }
+}
+
+// chunks [chunk0, chunk0 + count): the thread whose chunk is a parameter's first walks that parameter's chunks (adjacent, all inside the
+// range: a parameter lies in one segment) and adds their pairs in chunk order, in double, as optim_prepare_kernel adds the global norm.
+__global__ __launch_bounds__(OPT_THREADS) void lamb_fold_kernel(const OptChunk* __restrict__ table, int chunk0, int count,
+                                                                const float* __restrict__ pairs, const OptBlock* __restrict__ blk,
+                                                                float* __restrict__ ratio) {
+    if (blk->found_nonfinite) return;                          // the step is skipped: the stored ratios keep their bits
+    const int i = (int)blockIdx.x * OPT_THREADS + (int)threadIdx.x;
+    if (i >= count) return;
+    const int end = chunk0 + count, param = table[chunk0 + i].param;
+    if (!table[chunk0 + i].first) return;
+    double sw = 0.0, su = 0.0;
+    for (int k = chunk0 + i; k < end && table[k].param == param; ++k) {
+        sw += (double)pairs[2 * (long)k];
+        su += (double)pairs[2 * (long)k + 1];
+    }
+    ratio[param] = (sw > 0.0 && su > 0.0) ? (float)(sqrt(sw) / sqrt(su)) : 1.f;
+}
+
+// TRUST: LAMB's step with ratio[param] (else adamw_elem: adamw_kernel's bits in front of the clamp).  EMA: as adamw_ema_kernel.
+template <typename P, typename G, bool MASTER, bool TRUST, bool EMA>
+__global__ __launch_bounds__(OPT_THREADS) void optim_update_kernel(const OptChunk* __restrict__ table, int chunk0, float* __restrict__ exp_avg,
+                                                                   float* __restrict__ exp_avg_sq, float* __restrict__ master,
+                                                                   float* __restrict__ ema, const float* __restrict__ ratio,
+                                                                   const OptBlock* __restrict__ blk, int32_t* __restrict__ step_base,
+                                                                   UpdateArgs q, double ema_decay, int ema_warmup) {
+    const OptBlock b = *blk;
+    if (b.found_nonfinite) return;                             // the step is skipped
+    const OptChunk c = table[chunk0 + (int)blockIdx.x];
+    if ((c.dtypes & 0xff) != OptDtype<P>::CODE || ((c.dtypes >> 8) & 0xff) != OptDtype<G>::CODE) return;
+    const int tid = threadIdx.x;
+    int base = step_base[c.param];                             // (the parameter's own step count: as adamw_kernel)
+    if (base < 0) {
+        base = b.step - 1;
+        if (tid == 0 && c.first) step_base[c.param] = base;
+    }
+    const int t = b.step - base;
+    const double bc1 = 1.0 - opt_ipow(q.a.beta1, t), bc2 = 1.0 - opt_ipow(q.a.beta2, t);
+    const float step_size = (float)(q.a.lr / bc1), bc2_sqrt = (float)sqrt(bc2), clip = b.clip_coef;              // AdamW's
+    const float rbc1 = (float)(1.0 / bc1), rbc2_sqrt = (float)(1.0 / sqrt(bc2));                                 // LAMB's, as lamb_norm_kernel
+    const float lr_r = TRUST ? (float)(q.a.lr * (double)ratio[c.param]) : 0.f;
+    const double ramp = (1.0 + (double)b.step) / (10.0 + (double)b.step);
+    const float omd = EMA ? (float)(1.0 - (ema_warmup && ramp < ema_decay ? ramp : ema_decay)) : 0.f;
+
+    P* p = reinterpret_cast<P*>(c.p);
+    const G* g = reinterpret_cast<const G*>(c.g);
+    float* m = exp_avg + c.state_off;
+    float* v = exp_avg_sq + c.state_off;
+    float* e = EMA ? ema + c.state_off : nullptr;
+    float* w = MASTER ? master + c.state_off : reinterpret_cast<float*>(c.p);
+    const int nvec = (opt_aligned16(c.p) && opt_aligned16(c.g) && (c.state_off & 3) == 0) ? c.n / 8 : 0;
+    for (int i = tid; i < nvec; i += OPT_THREADS) {
+        const long o = (long)i * 8;
+        float gv[8], mv[8], vv[8], wv[8], ev[8];
+        opt_load8<true>(g + o, gv);
+        opt_load8<true>(m + o, mv);
+        opt_load8<true>(v + o, vv);
+        opt_load8<true>(w + o, wv);
+        if (EMA) opt_load8<true>(e + o, ev);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            if (TRUST) wv[j] -= lr_r * lamb_elem(gv[j], wv[j], mv[j], vv[j], q, clip, rbc1, rbc2_sqrt);
+            else adamw_elem(gv[j], wv[j], mv[j], vv[j], q.a, clip, step_size, bc2_sqrt);
+            wv[j] = opt_clamp(wv[j], q.lo, q.hi);
+            if (EMA) ema_elem(wv[j], ev[j], omd);
+        }
+        opt_store8<true>(m + o, mv);
+        opt_store8<true>(v + o, vv);
+        opt_store8<true>(w + o, wv);
+        if (EMA) opt_store8<true>(e + o, ev);
+        if (MASTER) opt_store8<true>(p + o, wv);               // (rounds to the parameter's storage type)
+    }
+    for (int i = nvec * 8 + tid; i < c.n; i += OPT_THREADS) {  // scalar tail / unaligned chunk
+        float wi = w[i], mi = m[i], vi = v[i];
+        if (TRUST) wi -= lr_r * lamb_elem(to_f32(g[i]), wi, mi, vi, q, clip, rbc1, rbc2_sqrt);
+        else adamw_elem(to_f32(g[i]), wi, mi, vi, q.a, clip, step_size, bc2_sqrt);
+        wi = opt_clamp(wi, q.lo, q.hi);
+        if (EMA) {
+            float ei = e[i];
+            ema_elem(wi, ei, omd);
+            e[i] = ei;
+        }
+        m[i] = mi;
+        v[i] = vi;
+        w[i] = wi;
+        if (MASTER) p[i] = from_f32<P>(wi);
     }
 }
 

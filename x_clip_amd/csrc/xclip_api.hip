@@ -2051,6 +2051,78 @@ int xclip_adamw_ema_step(const void* table, int64_t chunk0, int64_t count, int p
     return check_launch(__func__);
 }
 
+// param groups with trust_ratio / bounds (kernels/optim.h: lamb_norm_kernel, lamb_fold_kernel, optim_update_kernel)
+static bool update_args(UpdateArgs& q, double lr, double beta1, double beta2, double eps, double weight_decay, double lo, double hi) {
+    q.a = adamw_args(lr, beta1, beta2, eps, weight_decay);
+    q.wd = (float)weight_decay;
+    q.lo = (float)lo;
+    q.hi = (float)hi;
+    // the caller rounds the bounds to the parameter's storage type (lo up, hi down): a value float would round again is refused
+    return (double)q.lo == lo && (double)q.hi == hi && q.lo <= q.hi;
+}
+
+int xclip_lamb_norm(const void* table, int64_t chunk0, int64_t count, int p_dtype, int g_dtype, const float* exp_avg, const float* exp_avg_sq,
+                    const float* master, const void* state_block, const int32_t* step_base, double beta1, double beta2, double eps,
+                    double weight_decay, float* pairs, void* stream) {
+    XC_REQUIRE(dtype_ok(p_dtype) && dtype_ok(g_dtype), "bad dtype");
+    XC_REQUIRE(chunk0 >= 0 && count >= 0 && chunk0 + count < (1ll << 30), "bad chunk range");
+    XC_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0 && eps < 1e30 && weight_decay >= 0.0 &&
+               weight_decay < 1e30, "bad hyper-parameter");
+    if (count == 0) return 0;
+    XC_REQUIRE(table && exp_avg && exp_avg_sq && state_block && step_base && pairs && aligned16(table) && aligned16(exp_avg) &&
+               aligned16(exp_avg_sq), "null or misaligned pointer");
+    XC_REQUIRE(p_dtype == XCLIP_F32 || (master && aligned16(master)), "bf16 parameters need the fp32 master array");
+    UpdateArgs q;
+    update_args(q, 0.0, beta1, beta2, eps, weight_decay, 0.0, 0.0);
+    dim3 grid((unsigned)count), block(OPT_THREADS);
+    hipStream_t st = (hipStream_t)stream;
+#define XC_LAMB_NORM(P, G, M) hipLaunchKernelGGL((lamb_norm_kernel<P, G, M>), grid, block, 32, st, (const OptChunk*)table, (int)chunk0, exp_avg, exp_avg_sq, master, (const OptBlock*)state_block, step_base, q, pairs)
+    if (p_dtype == XCLIP_BF16) { if (g_dtype == XCLIP_BF16) XC_LAMB_NORM(bf16_t, bf16_t, true); else XC_LAMB_NORM(bf16_t, float, true); }
+    else                       { if (g_dtype == XCLIP_BF16) XC_LAMB_NORM(float, bf16_t, false); else XC_LAMB_NORM(float, float, false); }
+#undef XC_LAMB_NORM
+    return check_launch(__func__);
+}
+
+int xclip_lamb_fold(const void* table, int64_t chunk0, int64_t count, const float* pairs, const void* state_block, float* ratio,
+                    void* stream) {
+    XC_REQUIRE(chunk0 >= 0 && count >= 0 && chunk0 + count < (1ll << 30), "bad chunk range");
+    if (count == 0) return 0;
+    XC_REQUIRE(table && pairs && state_block && ratio && aligned16(table), "null or misaligned pointer");
+    hipLaunchKernelGGL(lamb_fold_kernel, dim3((unsigned)((count + OPT_THREADS - 1) / OPT_THREADS)), dim3(OPT_THREADS), 0, (hipStream_t)stream,
+                       (const OptChunk*)table, (int)chunk0, (int)count, pairs, (const OptBlock*)state_block, ratio);
+    return check_launch(__func__);
+}
+
+int xclip_optim_update(const void* table, int64_t chunk0, int64_t count, int p_dtype, int g_dtype, float* exp_avg, float* exp_avg_sq,
+                       float* master, const void* state_block, int32_t* step_base, double lr, double beta1, double beta2, double eps,
+                       double weight_decay, const float* ratio, double lo, double hi, float* ema, double ema_decay, int ema_warmup,
+                       void* stream) {
+    XC_REQUIRE(dtype_ok(p_dtype) && dtype_ok(g_dtype), "bad dtype");
+    XC_REQUIRE(chunk0 >= 0 && count >= 0 && chunk0 + count < (1ll << 31), "bad chunk range");
+    XC_REQUIRE(lr >= 0.0 && lr < 1e30 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0 && eps < 1e30 &&
+               weight_decay >= 0.0 && weight_decay < 1e30, "bad hyper-parameter");
+    XC_REQUIRE(!ema || (ema_decay >= 0.0 && ema_decay < 1.0), "ema_decay must be in [0, 1)");
+    UpdateArgs q;
+    XC_REQUIRE(update_args(q, lr, beta1, beta2, eps, weight_decay, lo, hi), "bounds must be float values with lo <= hi (-inf / +inf: none)");
+    if (count == 0) return 0;
+    XC_REQUIRE(table && exp_avg && exp_avg_sq && state_block && step_base && aligned16(table) && aligned16(exp_avg) && aligned16(exp_avg_sq) &&
+               (!ema || aligned16(ema)), "null or misaligned pointer");
+    XC_REQUIRE(p_dtype == XCLIP_F32 || (master && aligned16(master)), "bf16 parameters need the fp32 master array");
+    dim3 grid((unsigned)count), block(OPT_THREADS);
+    hipStream_t st = (hipStream_t)stream;
+#define XC_UPDATE(P, G, M, T, E) hipLaunchKernelGGL((optim_update_kernel<P, G, M, T, E>), grid, block, 0, st, (const OptChunk*)table, (int)chunk0, exp_avg, exp_avg_sq, master, ema, ratio, (const OptBlock*)state_block, step_base, q, ema_decay, ema_warmup ? 1 : 0)
+#define XC_UPDATE_PG(T, E)                                                                                                          \
+    do {                                                                                                                            \
+        if (p_dtype == XCLIP_BF16) { if (g_dtype == XCLIP_BF16) XC_UPDATE(bf16_t, bf16_t, true, T, E); else XC_UPDATE(bf16_t, float, true, T, E); } \
+        else                       { if (g_dtype == XCLIP_BF16) XC_UPDATE(float, bf16_t, false, T, E); else XC_UPDATE(float, float, false, T, E); } \
+    } while (0)
+    if (ratio) { if (ema) XC_UPDATE_PG(true, true); else XC_UPDATE_PG(true, false); }
+    else       { if (ema) XC_UPDATE_PG(false, true); else XC_UPDATE_PG(false, false); }
+#undef XC_UPDATE_PG
+#undef XC_UPDATE
+    return check_launch(__func__);
+}
+
 int xclip_grad_accumulate(const void* table, int64_t chunk0, int64_t count, int g_dtype, float* acc, int materialise, void* stream) {
     XC_REQUIRE(dtype_ok(g_dtype), "bad gradient dtype");
     XC_REQUIRE(chunk0 >= 0 && count >= 0 && chunk0 + count < (1ll << 31), "bad chunk range");

@@ -1683,3 +1683,42 @@ def grad_accumulate(table: Tensor, chunk0: int, count: int, grad_dtype, acc: Ten
     assert acc.dtype == torch.float32
     _lib.check(_lib.lib().xclip_grad_accumulate(table.data_ptr(), chunk0, count, _DTYPES[grad_dtype], acc.data_ptr(), int(bool(materialise)),
                                                 _stream(table)), "xclip_grad_accumulate")
+
+
+def lamb_norm(table: Tensor, chunk0: int, count: int, param_dtype, grad_dtype, exp_avg: Tensor, exp_avg_sq: Tensor, master: Optional[Tensor],
+              block: Tensor, step_base: Tensor, beta1: float, beta2: float, eps: float, weight_decay: float, pairs: Tensor) -> None:
+    """chunks [chunk0, chunk0 + count) of a `trust_ratio` group: pairs[c] = (sum w^2, sum u^2) of chunk c, u = LAMB's update direction
+    formed from the moments as this step will leave them; nothing else is written"""
+    _dev_check(table, exp_avg, exp_avg_sq, master, block, step_base, pairs)
+    assert table.dtype == torch.uint8 and table.numel() >= (chunk0 + count) * OPTIM_CHUNK_BYTES
+    assert exp_avg.dtype == torch.float32 and exp_avg_sq.dtype == torch.float32 and (master is None or master.dtype == torch.float32)
+    assert pairs.dtype == torch.float32 and pairs.numel() >= 2 * (chunk0 + count)
+    _lib.check(_lib.lib().xclip_lamb_norm(table.data_ptr(), chunk0, count, _DTYPES[param_dtype], _DTYPES[grad_dtype], exp_avg.data_ptr(),
+                                          exp_avg_sq.data_ptr(), _ptr(master), block.data_ptr(), step_base.data_ptr(), float(beta1),
+                                          float(beta2), float(eps), float(weight_decay), pairs.data_ptr(), _stream(table)), "xclip_lamb_norm")
+
+
+def lamb_fold(table: Tensor, chunk0: int, count: int, pairs: Tensor, block: Tensor, ratio: Tensor) -> None:
+    """ratio[parameter] = |w| / |u| (1 when either is 0) for every parameter whose chunks lie in [chunk0, chunk0 + count)"""
+    _dev_check(table, pairs, block, ratio)
+    assert table.dtype == torch.uint8 and table.numel() >= (chunk0 + count) * OPTIM_CHUNK_BYTES
+    assert pairs.dtype == torch.float32 and pairs.numel() >= 2 * (chunk0 + count) and ratio.dtype == torch.float32
+    _lib.check(_lib.lib().xclip_lamb_fold(table.data_ptr(), chunk0, count, pairs.data_ptr(), block.data_ptr(), ratio.data_ptr(), _stream(table)),
+               "xclip_lamb_fold")
+
+
+def optim_update(table: Tensor, chunk0: int, count: int, param_dtype, grad_dtype, exp_avg: Tensor, exp_avg_sq: Tensor, master: Optional[Tensor],
+                 block: Tensor, step_base: Tensor, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float,
+                 ratio: Optional[Tensor], lo: float, hi: float, ema: Optional[Tensor] = None, ema_decay: float = 0.0,
+                 ema_warmup: bool = False) -> None:
+    """`adamw_step` / `adamw_ema_step` (`ema`) for a group with a trust ratio (`ratio`: LAMB's step with ratio[parameter]) and / or
+    bounds: lo <= w <= hi on the fp32 weight after the step, before the EMA and the rounding (-inf / +inf: none; both exact in fp32)"""
+    _dev_check(table, exp_avg, exp_avg_sq, master, block, step_base, ratio, ema)
+    assert table.dtype == torch.uint8 and table.numel() >= (chunk0 + count) * OPTIM_CHUNK_BYTES
+    assert exp_avg.dtype == torch.float32 and exp_avg_sq.dtype == torch.float32 and (master is None or master.dtype == torch.float32)
+    assert ratio is None or ratio.dtype == torch.float32
+    assert ema is None or (ema.dtype == torch.float32 and ema.numel() == exp_avg.numel())
+    _lib.check(_lib.lib().xclip_optim_update(table.data_ptr(), chunk0, count, _DTYPES[param_dtype], _DTYPES[grad_dtype], exp_avg.data_ptr(),
+                                             exp_avg_sq.data_ptr(), _ptr(master), block.data_ptr(), step_base.data_ptr(), float(lr),
+                                             float(beta1), float(beta2), float(eps), float(weight_decay), _ptr(ratio), float(lo), float(hi),
+                                             _ptr(ema), float(ema_decay), int(bool(ema_warmup)), _stream(table)), "xclip_optim_update")

@@ -9,9 +9,11 @@ learning rates most updates are below half an ulp of the weight and are rounded 
 has (forward and backward are untouched); the optimizer owns an fp32 copy, updates that, and writes each parameter as its rounded value.
 Python does bookkeeping only: every number is computed by the HIP kernels, nothing is read back to the host during a step.
 `ema_decay=...` keeps an fp32 moving average of those unrounded weights in the same pass; `with opt.ema_weights():` evaluates on it.
+Param-group keys `trust_ratio` (LAMB's layer-wise step) and `bounds` (a clamp of the fp32 weight, e.g. CLIP's temperature) act on the masters.
 """
 from __future__ import annotations
 
+import math
 from contextlib import contextmanager
 from itertools import chain
 from typing import Optional
@@ -28,8 +30,39 @@ _TABLE_DTYPE = np.dtype([("p", "<u8"), ("g", "<u8"), ("state_off", "<i8"), ("n",
 assert _TABLE_DTYPE.itemsize == ops.OPTIM_CHUNK_BYTES
 _CODE = {torch.float32: 0, torch.bfloat16: 1}
 _STAGING = 4                                                    # pinned staging buffers per device (see _DeviceState)
-_GROUP_KEYS = ("lr", "betas", "eps", "weight_decay")           # what a param group means here
+_GROUP_KEYS = ("lr", "betas", "eps", "weight_decay", "trust_ratio", "bounds")       # what a param group means here
 _BLK_NORM, _BLK_CLIP, _BLK_BAD, _BLK_STEP, _BLK_SKIPPED = 0, 1, 2, 3, 4
+
+
+def _round_bound(x: float, dtype, up: bool) -> float:
+    """the value of `dtype` (fp32 / bf16) nearest to x on the side asked for (up: >= x, else <= x): a bound the stored weight can hold"""
+    f = np.float32(x)
+    if float(f) != x and (float(f) < x) == up:
+        f = np.nextafter(f, np.float32(np.inf if up else -np.inf))
+    if dtype == torch.bfloat16 and np.isfinite(f):
+        bits = int(f.view(np.uint32))
+        if bits & 0xffff:                                       # truncation rounds towards zero: one step away from it where that is asked for
+            bits = (bits & 0xffff0000) + (0x10000 if up == (f > 0) else 0)
+            f = np.uint32(bits).view(np.float32)
+    return float(f)
+
+
+def _group_bounds(group, dtype):
+    """(lo, hi) a group's `bounds` mean for weights stored as `dtype`: floats the kernels take, -inf / +inf where there is none"""
+    bounds = group.get("bounds")
+    if bounds is None:
+        return -math.inf, math.inf
+    try:
+        lo, hi = bounds
+        lo, hi = -math.inf if lo is None else float(lo), math.inf if hi is None else float(hi)
+    except (TypeError, ValueError):
+        raise ValueError(f"invalid bounds: {bounds!r} (None or a pair (lo, hi), either end None)") from None
+    if math.isnan(lo) or math.isnan(hi) or lo > hi or lo == math.inf or hi == -math.inf:
+        raise ValueError(f"invalid bounds: {bounds!r} (lo > hi)")
+    rlo, rhi = _round_bound(lo, dtype, True), _round_bound(hi, dtype, False)
+    if rlo > rhi:
+        raise ValueError(f"invalid bounds: {bounds!r} holds no {dtype} value (lo > hi after rounding lo up to {rlo!r} and hi down to {rhi!r})")
+    return rlo, rhi
 
 
 class _DeviceState:
@@ -51,6 +84,8 @@ class _DeviceState:
         self.ema = torch.zeros(max(off, 1), dtype=torch.float32, device=device) if ema else None      # (every parameter, fp32 ones too)
         self.block = torch.zeros(ops.OPTIM_BLOCK_WORDS, dtype=torch.int32, device=device)
         self.step_base = torch.full((max(len(self.params), 1),), -1, dtype=torch.int32, device=device)
+        self.ratio = torch.ones(max(len(self.params), 1), dtype=torch.float32, device=device)   # trust ratio of the last applied step
+        self.pairs = None                                       # (sum w^2, sum u^2) per chunk: allocated by the first `trust_ratio` step
         self.max_chunks = sum((p.numel() + ops.OPTIM_CHUNK - 1) // ops.OPTIM_CHUNK for p, _ in self.params)
         table_bytes = max(self.max_chunks, 1) * ops.OPTIM_CHUNK_BYTES
         # one buffer = the chunk table followed by the list of parameters without a gradient: one copy per rebuild
@@ -101,6 +136,17 @@ class FusedAdamW(torch.optim.Optimizer):
       the EMA bit-identical) and the applied step count u behind `ema_warmup` (d = min(ema_decay, (1 + u) / (10 + u)), timm's ramp).
       Initialised to the weights (exact); parameters without a gradient are not averaged.  `state[p]["ema"]` is a view of the flat array;
       `with opt.ema_weights():` evaluates or checkpoints the model on the averaged weights.
+    * param-group key `trust_ratio` (False; also a constructor default): LAMB as timm / apex state it -- the same moments, the update
+      u = (m / bc1) / (sqrt(v / bc2) + eps) + weight_decay w (decay INSIDE the update), and w -= lr r u with r = |w| / |u| over the whole
+      tensor (1 when either norm is 0), in fp32 on the master.  Two more launches per group: u's and w's sums of squares per chunk, and a
+      fold by parameter into a flat device array; `state[p]["trust_ratio"]` is a view of its entry (the r of the last applied step, 1
+      for parameters outside such a group).  Nothing is read back; a skipped step leaves the array alone.
+    * param-group key `bounds` (None; (lo, hi), either end None; also a constructor default): lo <= w <= hi on the fp32 weight right
+      after its update, before the EMA sees it and before the bf16 parameter is rounded from it.  It is here because a user's
+      `p.data.clamp_()` on a bf16 model reaches only the rounded copy, which the next step overwrites from the unclamped master.  For
+      a bf16 parameter lo is rounded up and hi down to bf16 once, so the parameter stays inside as well; lo > hi: ValueError.
+      Both keys are read at every step as `lr` is, travel in `state_dict()` and are absent from the groups of an optimizer that does
+      not use them.  A group with neither launches exactly the kernels it launched before they existed.
     * `accumulate_begin()` / `accumulate()` / `accumulate_end()` sum the gradients of several backward passes in a flat fp32 array
       (4 bytes per parameter, allocated at the first `accumulate_begin()`) and round the sum once into `.grad`; `step()` itself is
       unchanged and raises while a sum is open.  `x_clip_amd.cached.CachedContrastiveStep` is built on them.
@@ -115,7 +161,8 @@ class FusedAdamW(torch.optim.Optimizer):
     persistent slice only while `.grad` is None, and the re-created `.grad` has the same address, so the table stays valid."""
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
-                 max_grad_norm: Optional[float] = None, ema_decay: Optional[float] = None, ema_warmup: bool = True):
+                 max_grad_norm: Optional[float] = None, ema_decay: Optional[float] = None, ema_warmup: bool = True,
+                 trust_ratio: bool = False, bounds=None):
         if not 0.0 <= lr:
             raise ValueError(f"invalid learning rate: {lr}")
         if not 0.0 <= eps:
@@ -134,7 +181,17 @@ class FusedAdamW(torch.optim.Optimizer):
         self._accumulating = False                              # between accumulate_begin() and accumulate_end()
         self._accumulated = {}                                  # id(param) -> param: what accumulate() has taken a gradient from
         self._devs = None
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        # (off = the key is absent: the groups, and with them state_dict(), of an optimizer that uses neither are what they were)
+        if trust_ratio:
+            defaults["trust_ratio"] = True
+        if bounds is not None:
+            _group_bounds({"bounds": bounds}, torch.float32)    # (raises ValueError)
+            defaults["bounds"] = tuple(bounds)
+        super().__init__(params, defaults)
+        for group in self.param_groups:
+            for dtype in {p.dtype for p in group["params"]} & set(_CODE):
+                _group_bounds(group, dtype)                     # (raises ValueError)
         self.max_grad_norm = max_grad_norm
         self.table_uploads = 0                                  # chunk-table uploads so far (tests: none from the second GradSync step on)
         self._build()
@@ -170,6 +227,7 @@ class FusedAdamW(torch.optim.Optimizer):
                     if D.ema is not None:
                         st["ema"] = D.view(D.ema, i)
                         st["ema"].copy_(p)                      # (= the master of a bf16 parameter)
+                    st["trust_ratio"] = D.ratio[i]              # (a view: written on the device by a `trust_ratio` group's steps, else 1)
 
     def _one(self) -> _DeviceState:
         if len(self._devs) != 1:
@@ -270,7 +328,18 @@ class FusedAdamW(torch.optim.Optimizer):
                 ops.optim_prepare(D.partials, D.n_chunks, self.max_grad_norm, D.block, D.step_base, D.absent, D.n_absent)
                 for c0, n, gi, pc, gc in D.segments:
                     g = self.param_groups[gi]
-                    if D.ema is None:
+                    trust, (lo, hi) = bool(g.get("trust_ratio", False)), _group_bounds(g, dt[pc])
+                    if trust or lo != -math.inf or hi != math.inf:
+                        if trust:
+                            if D.pairs is None:
+                                D.pairs = torch.zeros(2 * max(D.max_chunks, 1), dtype=torch.float32, device=D.device)
+                            ops.lamb_norm(D.table, c0, n, dt[pc], dt[gc], D.exp_avg, D.exp_avg_sq, D.master, D.block, D.step_base,
+                                          g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], D.pairs)
+                            ops.lamb_fold(D.table, c0, n, D.pairs, D.block, D.ratio)
+                        ops.optim_update(D.table, c0, n, dt[pc], dt[gc], D.exp_avg, D.exp_avg_sq, D.master, D.block, D.step_base,
+                                         g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], D.ratio if trust else None,
+                                         lo, hi, D.ema, self.ema_decay or 0.0, self.ema_warmup)
+                    elif D.ema is None:
                         ops.adamw_step(D.table, c0, n, dt[pc], dt[gc], D.exp_avg, D.exp_avg_sq, D.master, D.block, D.step_base,
                                        g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"])
                     else:
@@ -396,7 +465,8 @@ class FusedAdamW(torch.optim.Optimizer):
     def state_dict(self):
         """`torch.optim.AdamW`'s layout (`step`, `exp_avg`, `exp_avg_sq` per parameter that has been stepped, fp32) plus `master` for bf16
         parameters, `ema` with `ema_decay` and, beside torch's two keys, `max_grad_norm`, `skipped_steps` (per device) and -- with `ema_decay`
-        only: a dict of an optimizer without it is what it was -- `ema_decay` / `ema_warmup`.  Copies (not views of the flat state);
+        only: a dict of an optimizer without it is what it was -- `ema_decay` / `ema_warmup`.  Param groups carry `trust_ratio` / `bounds`
+        where they have them, and the parameters of a `trust_ratio` group their last `trust_ratio`.  Copies (not views of the flat state);
         reads the step counts back: a checkpoint is a synchronisation point.  `register_state_dict_pre_hook` / `_post_hook` hooks run."""
         for hook in self._optimizer_state_dict_pre_hooks.values():
             hook(self)
@@ -421,6 +491,8 @@ class FusedAdamW(torch.optim.Optimizer):
                     st["master"] = D.view(D.master, i).clone()
                 if D.ema is not None:
                     st["ema"] = D.view(D.ema, i).clone()
+                if self.param_groups[D.params[i][1]].get("trust_ratio", False):
+                    st["trust_ratio"] = D.ratio[i].clone()
                 state[index[id(p)]] = st
         out = {"state": state, "param_groups": packed, "max_grad_norm": self.max_grad_norm,
                "skipped_steps": {str(D.device): int(D.block[_BLK_SKIPPED]) for D in self._devs.values()}}
@@ -435,7 +507,8 @@ class FusedAdamW(torch.optim.Optimizer):
     def load_state_dict(self, state_dict):
         """accepts state_dict() of this class and of `torch.optim.AdamW` (no `master`: the masters are initialised from the parameters).
         Not the base class's: that one casts floating-point state to the PARAMETER's dtype, which would round the fp32 moments and masters
-        of bf16 parameters to bf16.  Of a saved param group only lr / betas / eps / weight_decay are taken (torch's foreach, fused,
+        of bf16 parameters to bf16.  Of a saved param group only lr / betas / eps / weight_decay and -- where the dict has them: a
+        `torch.optim.AdamW` dict or an older one leaves this optimizer's -- trust_ratio / bounds are taken (torch's foreach, fused,
         capturable ... mean nothing here; amsgrad / maximize are refused); `skipped_steps` is restored when present.  With `ema_decay`:
         `ema` is restored where the dict has it and is otherwise the loaded master / parameter (a `torch.optim.AdamW` dict, a dict saved
         without EMA, a parameter never stepped); `ema_decay` / `ema_warmup` are taken from a dict that has them.  Without: a dict's EMA
@@ -452,6 +525,10 @@ class FusedAdamW(torch.optim.Optimizer):
             raise ValueError("x_clip_amd FusedAdamW has no amsgrad / maximize variant")
         for s, g in zip(saved, self.param_groups):
             g.update({k: s[k] for k in _GROUP_KEYS if k in s})
+            if g.get("bounds") is not None:
+                g["bounds"] = tuple(g["bounds"])
+            for dtype in {p.dtype for p in g["params"]} & set(_CODE):
+                _group_bounds(g, dtype)                         # (raises ValueError)
         if "max_grad_norm" in state_dict:
             self.max_grad_norm = state_dict["max_grad_norm"]
         if self.ema_decay is not None and state_dict.get("ema_decay") is not None:
@@ -476,6 +553,7 @@ class FusedAdamW(torch.optim.Optimizer):
                 if D.ema is not None:
                     weight = D.view(D.master, i) if p.dtype == torch.bfloat16 else p
                     D.view(D.ema, i).copy_(st["ema"] if st is not None and "ema" in st else weight)
+                D.ratio[i] = float(st["trust_ratio"]) if st is not None and "trust_ratio" in st else 1.0
             D.step_base.copy_(torch.tensor([-1 if s is None else total - s for s in steps] or [-1], dtype=torch.int32))
             D.block[_BLK_STEP] = total
             D.block[_BLK_SKIPPED] = int(state_dict.get("skipped_steps", {}).get(str(D.device), 0))
@@ -485,15 +563,28 @@ class FusedAdamW(torch.optim.Optimizer):
 
     # ---- helpers ----
     @staticmethod
-    def default_param_groups(model: torch.nn.Module, weight_decay: float = 1e-2):
-        """two groups: weight matrices with `weight_decay`; everything with ndim < 2 (LayerNorm gains, biases, cls token, temperature) and
-        the embedding tables without"""
+    def default_param_groups(model: torch.nn.Module, weight_decay: float = 1e-2, trust_ratio: bool = False, temperature_bounds=None):
+        """two groups: weight matrices with `weight_decay`; everything with ndim < 2 (LayerNorm gains, biases, cls token, temperature,
+        logit_bias) and the embedding tables without.  `trust_ratio=True`: the weight-matrix group carries it (LAMB), the other does not
+        -- the usual exclusion.  `temperature_bounds=(lo, hi)`: `model.temperature` moves into a third group: no decay, no trust ratio,
+        those bounds (CLIP's `logit_scale.clamp_(0, ln 100)`, applied to the fp32 master).  With the defaults: the two groups as ever."""
         tables = {id(m.weight) for m in model.modules() if isinstance(m, torch.nn.Embedding)}
+        temperature = None
+        if temperature_bounds is not None:
+            temperature = getattr(model, "temperature", None)
+            if not isinstance(temperature, torch.nn.Parameter) or not temperature.requires_grad:
+                raise ValueError("temperature_bounds: the model has no trainable parameter `temperature`")
         decay, plain = [], []
         for p in model.parameters():
-            if p.requires_grad:
+            if p.requires_grad and p is not temperature:
                 (plain if p.ndim < 2 or id(p) in tables else decay).append(p)
-        return [{"params": decay, "weight_decay": weight_decay}, {"params": plain, "weight_decay": 0.0}]
+        groups = [{"params": decay, "weight_decay": weight_decay}, {"params": plain, "weight_decay": 0.0}]
+        if trust_ratio:
+            groups[0]["trust_ratio"] = True
+            groups[1]["trust_ratio"] = False                    # (explicit: an optimizer built with trust_ratio=True leaves these alone too)
+        if temperature is not None:
+            groups.append({"params": [temperature], "weight_decay": 0.0, "trust_ratio": False, "bounds": tuple(temperature_bounds)})
+        return groups
 
 
 class _null:
